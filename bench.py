@@ -7,6 +7,13 @@ the reference's train_epoch (src/train_gnn.py:187-209): forward + masked weighte
 backward + clip_grad_norm_(1.0) + Adam; the loss stays on device (no per-step .item()).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--arch A] [--scale weak|strong]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line.  --dump-outputs DIR
+also writes what the last timed step computed (DIR/<name>.npy, float32: the loss, the logits,
+every parameter after the step and its gradient); the inputs and initial weights are seeded, so
+two builds run with the same arguments can be compared array for array.  --full adds the legs
+that take runs of their own after the timed region (``roofline``, ``cpu_baseline`` below).
 
 N > 1 (launched by torch.distributed.run, one rank per GPU): ONE global graph is partitioned
 by whole timesteps over the ranks (distributed.shard_graph: LPT bin-packing, no cross-timestep
@@ -19,7 +26,7 @@ loss is normalised by the global train count and BatchNorm (SAGE-ResBN) is SyncB
                  each), partitioned by (block, timestep): per-GPU work fixed.
 value = edges of the global graph x steps / max-over-ranks wall time.
 
-Extra fields: ``roofline`` (dominant libgnnmp kernel: algorithmic bytes per launch / its
+Extra fields (--full only, else null): ``roofline`` (dominant libgnnmp kernel: algorithmic bytes per launch / its
 HIP-event-timed average duration, on the launch stream) and ``cpu_baseline`` (the oracle —
 the PyG-2.5.3 ATen op sequence — timed on this host's cores, rank 0 at N=1 only, bounded
 sample; all usable physical cores and a 1-thread figure, with the host's model/sockets/cores).
@@ -71,9 +78,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--degree", default="powerlaw", choices=["powerlaw", "uniform"])
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: the roofline "
+                         "(instrumented eager steps) and the CPU baseline; off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): "
+                         "loss, logits, every parameter after the step and its gradient")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel from Python each step (default: replay the step as captured "
                          "HIP graphs; N>1: forward+backward graph, eager all-reduce, optimizer graph)")
@@ -462,6 +475,8 @@ def main():
 
     from elliptic_gnn_project_amd.train_ops import unit_gradient
 
+    kept = {} if args.dump_outputs else None
+
     def fwd_bwd():
         model.train()
         opt.zero_grad(set_to_none=bucket is None)
@@ -475,6 +490,8 @@ def main():
         else:  # the same masked weighted CE, one fused kernel (fwd + dlogits)
             loss = loss_fn.full(logits, data.y, data.train_mask, denom=denom)
         loss.backward(unit_gradient(loss.device))  # = loss.backward(), without the per-step fill
+        if kept is not None:  # --dump-outputs: the step's logits stay readable after it
+            kept["logits"] = logits.detach()
         return loss.detach()  # drop the autograd graph now (a live one would pin this step's streams)
 
     def allreduce():
@@ -503,9 +520,9 @@ def main():
         step = eager_step
 
     def extras(value):
-        """roofline (instrumented eager steps) and the CPU baseline, after the timed region."""
+        """--full: roofline (instrumented eager steps) and the CPU baseline, after the timed region."""
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             KernelTimer.start()
             for _ in range(5):
                 # hold the stream in a spin kernel while Python enqueues the whole step, so each event
@@ -520,15 +537,49 @@ def main():
                                        "boundary (~1.5-3 us), which rocprofv3's kernel durations exclude")
 
         cpu = None
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(data_cpu, state0, cw.cpu(), denom, cfg, args.cpu_seconds, args.cpu_1t_seconds)
             cpu["speedup_gpu_over_cpu"] = round(value / cpu["value"], 1)
         return roof, cpu
 
+    def dump(loss):
+        """--dump-outputs: what the last timed step left its caller — the loss it returned, its logits,
+        every parameter (and float buffer) after the optimizer step and the gradient it stepped on —
+        as float32 .npy files (rank 0's copy at N > 1)."""
+        arrays = {"loss": loss, "logits": kept["logits"]}
+        for k, p in model.named_parameters():
+            arrays["param." + k] = p.detach()
+            if p.grad is not None:
+                arrays["grad." + k] = p.grad
+        for k, b in model.named_buffers():
+            if b.is_floating_point():
+                arrays["buffer." + k] = b
+        write_outputs(args.dump_outputs, arrays)
+
     launch = ("eager" if not use_graph else "hip-graph replay of the whole step" if bucket is None
               else "hip-graph replay of the whole step, RCCL collectives captured" if rccl
               else "hip-graph replay of fwd+bwd and of the optimizer, eager all-reduce between")
-    return report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf16, extras, launch)
+    return report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf16, extras, launch,
+                  dump=dump if args.dump_outputs and rank == 0 else None)
+
+
+DUMP_MAX_ELEMS = 4 << 20  # per array (16 MiB of float32); the step's outputs total far below 64 MB
+
+
+def write_outputs(outdir, arrays):
+    """Write each tensor as outdir/<name>.npy in float32.  An array above DUMP_MAX_ELEMS is cut to
+    a fixed sample of its flattened elements (seeded permutation, ascending index order), the same
+    on every run."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().to("cpu", torch.float32).contiguous()
+        if t.numel() > DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=gen)[:DUMP_MAX_ELEMS].sort().values
+            t = t.view(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), t.numpy())
 
 
 def settle(dev, ms: float):
@@ -556,9 +607,9 @@ def settle(dev, ms: float):
 
 
 def report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf16, extras, launch,
-           launch_check=False):
-    """Warm-up, the timed region (barrier + synchronize on both sides, max over ranks), and rank
-    0's JSON line."""
+           launch_check=False, dump=None):
+    """Warm-up, the timed region (barrier + synchronize on both sides, max over ranks), the dump of
+    the last timed step's outputs (``dump``, before any further step runs) and rank 0's JSON line."""
     sync = torch.cuda.synchronize if dev.type == "cuda" else (lambda: None)
     settled = settle(dev, args.settle_ms)
     for _ in range(args.warmup):
@@ -567,7 +618,7 @@ def report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf1
         dist.barrier()
     sync()
     trace = args.step_trace and dev.type == "cuda"
-    evs, host = [], []
+    evs, host, last = [], [], None
     if trace:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
@@ -575,7 +626,7 @@ def report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf1
         if trace:
             evs[i].record()
             host.append(time.perf_counter())
-        step()
+        last = step()
     if trace:
         evs[-1].record()
     sync()
@@ -597,6 +648,8 @@ def report(args, preset, full, E_global, data, dist, world, rank, dev, step, bf1
         dist.all_reduce(nl, op=dist.ReduceOp.MAX)
         n_local = nl.cpu()
     value = E_global * args.steps / el
+    if dump is not None and args.steps > 0:
+        dump(last)
     roof, cpu = extras(value) if extras is not None else (None, None)
     if rank == 0:
         # the scale mode the N-GPU lines of the same command use (at N = 1 both modes run the one

@@ -11,8 +11,8 @@ timeout -k 10 400 python -u -m pytest -q --timeout 300 --timeout-method thread -
 rc=$?
 tail -3 "$OUT/t.txt"
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --arch sage_scaled --no-cpu-baseline > "$OUT/pad.log" 2>&1 || exit 1
-GNNMP_K1_PAD=0 timeout -k 10 300 python bench.py --arch sage_scaled --no-cpu-baseline > "$OUT/nopad.log" 2>&1 || exit 1
+timeout -k 10 300 python bench.py --full --arch sage_scaled --no-cpu-baseline > "$OUT/pad.log" 2>&1 || exit 1
+GNNMP_K1_PAD=0 timeout -k 10 300 python bench.py --full --arch sage_scaled --no-cpu-baseline > "$OUT/nopad.log" 2>&1 || exit 1
 for f in pad nopad; do python3 -c "
 import json; d=json.loads(open('$OUT/$f.log').read().strip().splitlines()[-1])
 t=d['roofline']['timed_kernels']; print('$f', round(d['ms_per_step'],4), {k: v['us_per_launch'] for k,v in t.items() if 'agg' in k})"; done

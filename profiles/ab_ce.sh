@@ -12,7 +12,7 @@ if [ $rc -ne 0 ]; then exit $rc; fi
 for i in 1 2 3; do
   for v in fused separate; do
     f=""; [ $v = separate ] && f="--separate-ce"
-    timeout -k 10 300 python bench.py --no-cpu-baseline --steps 50 --warmup 10 $f > "$OUT/b_$v$i.json" 2>> "$OUT/bench.err" || exit $?
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 50 --warmup 10 $f > "$OUT/b_$v$i.json" 2>> "$OUT/bench.err" || exit $?
     python3 -c "import json; d=json.load(open('$OUT/b_$v$i.json')); print('$v', round(d['ms_per_step'],4))"
   done
 done

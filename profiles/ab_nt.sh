@@ -7,7 +7,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for i in 1 2 3; do
   for v in 0 1; do
-    GNNMP_AB_NT32=$v timeout -k 10 200 python bench.py --steps 50 --warmup 10 --no-cpu-baseline > "$OUT/ab_$v_$i.json" 2>/dev/null || exit $?
+    GNNMP_AB_NT32=$v timeout -k 10 200 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline > "$OUT/ab_$v_$i.json" 2>/dev/null || exit $?
     python3 -c "import json; d=json.load(open('$OUT/ab_$v_$i.json')); t=d['roofline']['timed_kernels']; print('nt32=$v', round(d['ms_per_step'],4), [ (k[:14], v['us_per_launch']) for k,v in t.items() if 'gemm' in k])"
   done
 done

@@ -8,7 +8,7 @@ shift
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for ARCH in "$@"; do
-  timeout -k 10 300 python bench.py --arch "$ARCH" > "$OUT/bench_$ARCH.log" 2>&1
+  timeout -k 10 300 python bench.py --full --arch "$ARCH" > "$OUT/bench_$ARCH.log" 2>&1
   tail -1 "$OUT/bench_$ARCH.log" > "$OUT/bench_$ARCH.json"
   python3 -c "import json,sys; d=json.load(open('$OUT/bench_$ARCH.json')); print('$ARCH', round(d['ms_per_step'],4), 'ms', round(d['value']/1e6,1), 'M edges/s')"
 done

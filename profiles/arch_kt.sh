@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 for ARCH in "$@"; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt_$ARCH" -o run --output-format csv \
-      -- python3 bench.py --arch "$ARCH" --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/kt_$ARCH.log" 2>&1
+      -- python3 bench.py --full --arch "$ARCH" --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/kt_$ARCH.log" 2>&1
   find "$OUT/kt_$ARCH" -name "*kernel_stats.csv" -exec cp {} "$OUT/${ARCH}_kernel_stats.csv" \;
   tail -1 "$OUT/kt_$ARCH.log"
 done

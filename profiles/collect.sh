@@ -13,7 +13,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 BENCH="bench.py --arch $ARCH --steps 20 --warmup 5 --no-cpu-baseline"
 
-timeout -k 10 420 python bench.py --arch $ARCH > "$OUT/bench.log" 2>&1
+timeout -k 10 420 python bench.py --full --arch $ARCH > "$OUT/bench.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o run --output-format csv \
     -- python3 $BENCH > "$OUT/kt.log" 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o run --output-format csv \

@@ -9,7 +9,7 @@ timeout -k 10 420 python -u -m pytest tests/test_gpu_tn_csc.py tests/test_gpu_fu
 tail -3 $OUT/pytest_csc.txt
 for rep in 1 2; do
   for v in 1 0; do
-    GNNMP_TN_CSC=$v timeout -k 10 200 python bench.py --no-cpu-baseline > $OUT/bench_csc${v}_$rep.json 2>$OUT/bench_csc${v}_$rep.err || exit $?
+    GNNMP_TN_CSC=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline > $OUT/bench_csc${v}_$rep.json 2>$OUT/bench_csc${v}_$rep.err || exit $?
     GNNMP_TN_CSC=$v timeout -k 10 200 python bench.py --rehearse-shard 8 --no-cpu-baseline --no-roofline > $OUT/shard8_csc${v}_$rep.json 2>/dev/null || exit $?
     python3 -c "import json; a=json.load(open('$OUT/bench_csc${v}_$rep.json')); b=json.load(open('$OUT/shard8_csc${v}_$rep.json')); print('TN_CSC=$v rep $rep: full', round(a['ms_per_step'],4), 'ms (frac', a['roofline']['frac'], ') shard8', round(b['ms_per_step'],4), 'ms')"
   done

@@ -14,7 +14,7 @@ for rep in 1 2; do
     done
   done
   for v in 1 0; do
-    GNNMP_TN_CSC_INKERNEL=$v timeout -k 10 200 python bench.py --no-cpu-baseline > $OUT/full_k${v}_$rep.json 2>/dev/null || exit $?
+    GNNMP_TN_CSC_INKERNEL=$v timeout -k 10 200 python bench.py --full --no-cpu-baseline > $OUT/full_k${v}_$rep.json 2>/dev/null || exit $?
     python3 -c "import json; a=json.load(open('$OUT/full_k${v}_$rep.json')); print('rep $rep full inkernel=$v', round(a['ms_per_step'],4), 'ms frac', a['roofline']['frac'])"
   done
 done

@@ -14,5 +14,5 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q -rfs --timeout 600 --timeo
 rc=$?
 tail -25 "$OUT/pytest_gpu.txt"
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then echo "suite rc=$rc: stopping"; exit $rc; fi
-timeout -k 10 420 python bench.py > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 420 python bench.py --full > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"

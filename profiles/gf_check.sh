@@ -10,7 +10,7 @@ rc=$?
 tail -3 "$OUT/pytest.txt"
 if [ $rc -ne 0 ]; then exit $rc; fi
 for arch in ${ARCHS:-gcn gat sage_resbn}; do
-  timeout -k 10 300 python bench.py --arch $arch --no-cpu-baseline --steps 30 --warmup 10 > "$OUT/$arch.json" 2>> "$OUT/err.txt" || exit $?
+  timeout -k 10 300 python bench.py --full --arch $arch --no-cpu-baseline --steps 30 --warmup 10 > "$OUT/$arch.json" 2>> "$OUT/err.txt" || exit $?
   python3 -c "
 import json; d=json.load(open('$OUT/$arch.json')); r=d['roofline']
 tn=[(k,v['us_per_launch']) for k,v in r['timed_kernels'].items() if 'tn' in k]

@@ -11,5 +11,5 @@ timeout -k 10 ${SUITE_LIMIT:-600} python -u -m pytest $SEL -m gpu -q -rfs -x --t
 rc=$?
 tail -25 "$OUT/pytest_gpu.txt"
 if [ $rc -ne 0 ]; then echo "suite rc=$rc: stopping"; exit $rc; fi
-timeout -k 10 420 python bench.py > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
+timeout -k 10 420 python bench.py --full > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; exit 1; }
 tail -1 "$OUT/bench.log"

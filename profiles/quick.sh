@@ -12,10 +12,10 @@ timeout -k 10 600 python -u -m pytest $TESTS -m gpu -x -q -rf --timeout 300 --ti
 rc=$?
 tail -4 "$OUT/pytest.txt"
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 300 python bench.py --arch $ARCH --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
+timeout -k 10 300 python bench.py --full --arch $ARCH --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']; print('ms/step', round(d['ms_per_step'],4), 'dominant', r['kernel'], r['avg_us'], r['frac']); [print('  ', k, v['us_per_launch'], v.get('hbm_frac')) for k,v in r['timed_kernels'].items()]"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -o run --output-format csv \
-    -- python3 bench.py --arch $ARCH --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/kt.log" 2>&1 || exit $?
+    -- python3 bench.py --full --arch $ARCH --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/kt.log" 2>&1 || exit $?
 find "$OUT" -name "*kernel_stats.csv" -exec cp {} "$OUT/kernel_stats.csv" \;
 python3 -c "
 import csv

@@ -10,6 +10,6 @@ rc=$?
 tail -4 "$OUT/pytest_gpu.txt"
 if [ $rc -ne 0 ]; then exit $rc; fi
 for arch in "$@"; do
-  timeout -k 10 300 python bench.py --arch $arch --no-cpu-baseline --steps 50 --warmup 10 > "$OUT/$arch.json" 2>> "$OUT/err.txt" || exit $?
+  timeout -k 10 300 python bench.py --full --arch $arch --no-cpu-baseline --steps 50 --warmup 10 > "$OUT/$arch.json" 2>> "$OUT/err.txt" || exit $?
   python3 -c "import json; d=json.load(open('$OUT/$arch.json')); print('$arch', round(d['ms_per_step'],4))"
 done

@@ -12,5 +12,5 @@ run drv_settle --gpus 1 --steps 20 --warmup 5 $NC --step-trace
 run drv_nosettle --gpus 1 --steps 20 --warmup 5 $NC --settle-ms 0 --step-trace
 run long_settle --gpus 1 --steps 50 --warmup 10 $NC
 run drv_settle2 --gpus 1 --steps 20 --warmup 5 $NC --step-trace
-run drv_full --gpus 1 --steps 20 --warmup 5
+run drv_full --gpus 1 --steps 20 --warmup 5 --full
 grep step-trace "$OUT"/*.err | grep "gpu ms"
