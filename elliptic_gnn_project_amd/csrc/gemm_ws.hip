@@ -767,7 +767,17 @@ constexpr Sched make(int QP, int ne2, int nslot) {
 }
 }  // namespace h2s
 
-template <int NKS, int EPI, int LAB = 0>
+// INB (csrc/lab only, lab_inb.hip; the library instantiates 0 — it did not pay, DESIGN "experiments
+// that did not pay"): the prologue forms the lane's B fragments and its column scale from the
+// Linear weights themselves instead of loading the prep's image — column n of B is row n of
+// [W_l | pad | W_r | pad], so every value of lane (c, kh) lives in its own weight row, and its one
+// partner lane ^ 32 holds the column's other half: the column max is one shuffle.  The lane's 168
+// raw values are loaded at once (before the main loop's state is live), then converted per k-step
+// with the same per-element arithmetic as ws_prep_h2_cols (v · 2^-e_n, split_h2_pair,
+// h2_scale_pair), so the fragments and cs are the image's, bit for bit.  Needs even k1, k2, ldw
+// and 8-byte aligned weights (NTArgs.wvec2: 8-byte pair loads); bimg / colscale are not read.
+// 223-225 VGPRs + 252 AGPRs, no scratch, one wave per SIMD (the image form: 168-202 + 252).
+template <int NKS, int EPI, int LAB = 0, int INB = 0>
 __global__ __launch_bounds__(256) void gemm_nt_h2_kernel(NTArgs a, const uint4* __restrict__ bimg,
                                                          const float* __restrict__ colscale, int ntiles) {
   constexpr int PLB = NKS * WS_KSB;  // bytes per plane of an A buffer
@@ -787,7 +797,55 @@ __global__ __launch_bounds__(256) void gemm_nt_h2_kernel(NTArgs a, const uint4* 
   const uint64_t seed = a.seed_ptr ? (*a.seed_ptr) * 0x9E3779B97F4A7C15ull + a.seed : a.seed;
 
   f16x8 bw[NKS][3];  // hi' = 2^11 hi, hi, lo
-  {
+  float cs_inb = 0.f;  // INB: this lane's column scale, 2^(e_n - 11 - ap_exp)
+  if constexpr (INB != 0) {
+    const int n = 32 * wave + (lane & 31), kh = lane >> 5;
+    const bool live = n < a.Nc;
+    const int nc = live ? n : 0;
+    const float2* r1 = reinterpret_cast<const float2*>(a.w1 + (int64_t)nc * a.ldw1);
+    const float2* r2 = reinterpret_cast<const float2*>(a.k2 > 0 ? a.w2 + (int64_t)nc * a.ldw2 : a.w1 + (int64_t)nc * a.ldw1);
+    const int h1 = a.k1 >> 1, h2 = a.k2 >> 1, c2 = a.ap_col2 >> 1;  // in pairs of columns
+    // pair j of the lane's piece of k-step s: image columns 16s + 8kh + 2j, + 1 (col2 % 8 == 0: a
+    // piece lies on one side of col2); index clamped, the excess masked to 0
+    auto ldpair = [&](int s, int j) __attribute__((always_inline)) {
+      const int q0 = 8 * s + 4 * kh;
+      const bool left = q0 < c2;
+      const int i = (left ? q0 : q0 - c2) + j, lim = left ? h1 : h2;
+      const float2 v = (left ? r1 : r2)[max(min(i, lim - 1), 0)];
+      return (live && i < lim) ? v : make_float2(0.f, 0.f);
+    };
+    // every load issued before the first use (one round trip; nothing else is live yet)
+    float2 raw[NKS][4];
+#pragma unroll
+    for (int s = 0; s < NKS; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) raw[s][j] = ldpair(s, j);
+    __builtin_amdgcn_sched_barrier(0);
+    float m = 0.f;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m = fmaxf(m, fmaxf(fabsf(raw[s][j].x), fabsf(raw[s][j].y)));
+    m = fmaxf(m, __shfl_xor(m, 32));
+    const float sc = live ? h2_col_exp2(m) : 1.0f;
+    cs_inb = live ? sc * (1.0f / 2048.0f) * ldexpf(1.0f, -a.ap_exp) : 0.f;  // powers of two: exact
+    const float inv = 1.0f / sc;
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      uint32_t hw[4], lw[4], pw[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        split_h2_pair(raw[s][j].x * inv, raw[s][j].y * inv, hw[j], lw[j]);
+        pw[j] = h2_scale_pair(hw[j], 2048.0f);
+      }
+      bw[s][0] = __builtin_bit_cast(f16x8, make_uint4(pw[0], pw[1], pw[2], pw[3]));
+      bw[s][1] = __builtin_bit_cast(f16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
+      bw[s][2] = __builtin_bit_cast(f16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
+      // into its AGPRs now: the raw values' VGPRs are the main loop's
+      asm volatile("" : "+a"(bw[s][0]), "+a"(bw[s][1]), "+a"(bw[s][2]));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
     const int slot = 2 * (32 * wave + (lane & 31)) + (lane >> 5);
 #pragma unroll
     for (int s = 0; s < NKS; ++s)
@@ -826,7 +884,7 @@ __global__ __launch_bounds__(256) void gemm_nt_h2_kernel(NTArgs a, const uint4* 
   }
   float bv = 0.f;
   if constexpr ((EPI & WS_BIAS) != 0) bv = colok ? a.bias[col] : 0.f;
-  const float cs = colok ? colscale[col] : 0.f;  // 2^(e_n - 11)
+  const float cs = INB != 0 ? cs_inb : (colok ? colscale[col] : 0.f);  // 2^(e_n - 11 - ap_exp)
   float* const cptr = a.c;
   const int64_t ldc = a.ldc;
   const __amdgpu_buffer_rsrc_t crsrc =

@@ -46,6 +46,10 @@ _KEEP_MASK = os.environ.get("GNNMP_KEEP_MASK", "0") == "1"
 # The SAGE layer-0 half-pair NT's weight prep (its B image) rides in K1's launch on extra blocks
 # beside the gather (gnn_sage_mean_fwd_h2 prep_b); GNNMP_K1_PREP=0 leaves it to the NT call (A/B)
 _K1_PREP = os.environ.get("GNNMP_K1_PREP", "1") != "0"
+# The agg half of the layer-0 image is written once per registered x and graph plan
+# (planes.SplitImage.mean_cached): K1 leaves the steady-state step.  GNNMP_AGG_CACHE=0 runs K1 on
+# every forward — the step of an input that is not constant (A/B)
+_AGG_CACHE = os.environ.get("GNNMP_AGG_CACHE", "1") != "0"
 # K1 gathers a zero-padded copy of the registered x (rows of col2 = 168 floats, 16-byte pieces,
 # one pass per row, cached on x) instead of x itself (8-byte pieces, two passes): K1 107.0 ->
 # 92.5 us, the headline step 0.3426 -> 0.3299 ms (profiles/r19n_ab.txt).  GNNMP_K1_PAD=0: A/B
@@ -366,30 +370,34 @@ def gemm_tn_input(nr: int, x: torch.Tensor, g: torch.Tensor):
     return gemm_tn(nr, x, g=g)
 
 
-def _layer0_image(x: torch.Tensor, n_out: int, nt_kw, h2: bool = False):
+def _layer0_image(x: torch.Tensor, n_out: int, nt_kw, h2: bool = False, plan=None):
     """The split image of [agg | x] when the planes path takes this layer (else None): x must be a
     registered constant input (planes.register_input) — its planes are built once and reused; a
     per-batch or per-step input keeps the in-kernel split (gemm_nt over f32 [agg | x]).
     h2: prefer the half-pair image (f16 hi / lo planes, 3 products) when x fits it (finite)
-    — the 2-layer net, whose layer-0 weight gradient is the TN's dz form."""
+    — the 2-layer net, whose layer-0 weight gradient is the TN's dz form.
+    plan: the forward's graph plan — None too when a captured step reads the image's agg half
+    as another plan's means on every replay (SplitImage.agg_foreign): this forward must not
+    overwrite it."""
     if not (_PLANES and is_registered(x) and mean_planes_ok(x)) or x.size(0) < 32:
         return None
     if h2 and _H2 and HalfPairImage.addressable(x.size(0), x.size(1), x.size(1)) and h2_ok(x):
         im = x_image(x, HalfPairImage)
         if gemm_nt(None, None, n_out, planes=im, check_planes=True, **nt_kw):
-            return im
+            return None if (plan is not None and im.agg_foreign(plan)) else im
     if not SplitImage.addressable(x.size(0), x.size(1), x.size(1)):
         return None
     im = x_image(x)
     if not gemm_nt(None, None, n_out, planes=im, check_planes=True, **nt_kw):
         return None
-    return im
+    return None if (plan is not None and im.agg_foreign(plan)) else im
 
 
-def _bf_image0(x: torch.Tensor, L: int, Wl):
+def _bf_image0(x: torch.Tensor, L: int, Wl, plan=None):
     """The cached layer-0 bf16 image when every hidden layer's NT can run on images (the shapes
     nt_img16_ok takes: image rows of 256 or 336 columns, 8 <= F_out <= 128 with F_out % 8 == 0,
-    31-bit byte offsets), else None (the tiled bf16 NT over separate operands)."""
+    31-bit byte offsets), else None (the tiled bf16 NT over separate operands) — also when a
+    captured step reads its agg half as another plan's means (BfImage.agg_foreign)."""
     if not _BF_IMAGE or L < 2 or x.dim() != 2 or x.size(0) < 32 or x.stride(1) != 1:
         return None
     n, fi = x.size(0), x.size(1)
@@ -401,7 +409,8 @@ def _bf_image0(x: torch.Tensor, L: int, Wl):
         if n * max(ld, fo) * 2 >= 2 ** 31 or n * 4 * 4 >= 2 ** 31:
             return None
         fi = fo
-    return bf_x_image(x)
+    im = bf_x_image(x)
+    return None if (plan is not None and im.agg_foreign(plan)) else im
 
 
 class _FusedSAGE(torch.autograd.Function):
@@ -422,7 +431,7 @@ class _FusedSAGE(torch.autograd.Function):
         aggs = []
         z = None
         ctx.image = None
-        bim = _bf_image0(x, L, Wl) if x.dtype == torch.bfloat16 else None
+        bim = _bf_image0(x, L, Wl, plan) if x.dtype == torch.bfloat16 else None
         ctx.bimgs = [None] * (L - 1)
         for l in range(L - 1):
             h = hs[-1]
@@ -438,22 +447,28 @@ class _FusedSAGE(torch.autograd.Function):
                 nxt = BfImage(h.size(0), fo, fo, h.device) if not last_hidden else None
                 out = nxt.a2 if nxt is not None else torch.empty((h.size(0), fo), dtype=torch.bfloat16,
                                                                   device=h.device)
-                if _K1_PAD and bim.k2 == bim.k1 < bim.col2 and bim.col2 % 4 == 0 and bim.ld >= 2 * bim.col2:
-                    # h is the image's A2 half, zero columns up to ld (a padded image is zero-
-                    # allocated): gather it there at the padded width, 8-byte pieces in one pass
-                    # per row; the padding columns aggregate to the zeros already in A1's
-                    aggregate(plan, bim.img[:, bim.col2: 2 * bim.col2], _lib.AGG_MEAN, nodew=plan.deg,
-                              out=bim.img[:, : bim.col2])
+                def k1(bim=bim, h=h):
+                    if _K1_PAD and bim.k2 == bim.k1 < bim.col2 and bim.col2 % 4 == 0 and bim.ld >= 2 * bim.col2:
+                        # h is the image's A2 half, zero columns up to ld (a padded image is zero-
+                        # allocated): gather it there at the padded width, 8-byte pieces in one pass
+                        # per row; the padding columns aggregate to the zeros already in A1's
+                        aggregate(plan, bim.img[:, bim.col2: 2 * bim.col2], _lib.AGG_MEAN, nodew=plan.deg,
+                                  out=bim.img[:, : bim.col2])
+                    else:
+                        aggregate(plan, h, _lib.AGG_MEAN, nodew=plan.deg, out=bim.a1)
+
+                if l == 0:  # the cached image of a constant x: its agg half once per x and plan
+                    bim.mean_cached(plan, h, k1, cache=_AGG_CACHE)
                 else:
-                    aggregate(plan, h, _lib.AGG_MEAN, nodew=plan.deg, out=bim.a1)
+                    k1()
                 hn = gemm_nt(None, None, fo, planes=bim, out=out, **nt_kw)
                 ctx.bimgs[l] = bim
                 aggs.append(bim.a1)
                 hs.append(hn)
                 bim = nxt
                 continue
-            im = _layer0_image(h, Wl[0].size(0), nt_kw, h2=last_hidden) if l == 0 else None
-            if im is not None:  # agg written straight into the split image by K1; A staged as planes
+            im = _layer0_image(h, Wl[0].size(0), nt_kw, h2=last_hidden, plan=plan) if l == 0 else None
+            if im is not None:  # agg in the split image (K1, once per x and plan); A staged as planes
                 keep = None
                 if isinstance(im, HalfPairImage) and train_drop > 0 and _KEEP_MASK:  # K1 also writes the NT's keep bits
                     kb = im.keep_buffer()
@@ -462,9 +477,8 @@ class _FusedSAGE(torch.autograd.Function):
                 n_out = Wl[l].size(0)
                 ws, side, ready = _nt_workspace(h.device, n_out, im.k1, im.k2), None, False
                 prep_b = None
-                if _K1_PREP and isinstance(im, HalfPairImage):  # the B prep inside K1's launch
-                    prep_b = gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="params", **nt_kw)
-                    ready = True
+                if _K1_PREP and isinstance(im, HalfPairImage):  # the B prep inside K1's launch, when K1 runs
+                    prep_b = lambda: gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="params", **nt_kw)  # noqa: E731
                 elif _SIDE_PREP:  # the B prep beside K1 on a side stream (it reads only the weights)
                     side, cur = _side_stream(h.device), torch.cuda.current_stream(h.device)
                     side.wait_stream(cur)
@@ -472,9 +486,13 @@ class _FusedSAGE(torch.autograd.Function):
                         gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="prep", **nt_kw)
                     ready = True
                 xp = x_padded(h, im.col2) if _K1_PAD and im.col2 % 4 == 0 and im.col2 > h.size(1) else None
-                ctx.image = (im, im.fill_mean(plan, h, keep, prep_b=prep_b, x_pad=xp))
+                gen, hit = im.mean_cached(plan, h, keep, prep_b=prep_b, x_pad=xp, cache=_AGG_CACHE)
+                ctx.image = (im, gen)
                 if side is not None:
                     cur.wait_stream(side)
+                if prep_b is not None and not hit:
+                    ready = True  # the prep rode in K1's launch
+                # not ready (a hit: no K1 to ride in): the NT call launches its own B-image prep
                 hn = gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="ready" if ready else None, **nt_kw)
                 agg = None
             else:

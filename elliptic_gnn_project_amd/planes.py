@@ -5,23 +5,32 @@ The split-bf16 GEMMs run every f32 operand as three bf16 terms, v = hi + mid + l
 ~5.5 VALU per element, twice per step for the [N, 332] layer-1 operand.  A ``SplitImage`` holds
 the three planes in HBM instead ([3, N, ld] bf16, include/gnnmp.h gnn_split_planes_f32):
 
-    columns [0, k1)               agg = mean_{j->i} x[j]   K1 writes them every forward
-                                                           (gnn_sage_mean_fwd_planes)
+    columns [0, k1)               agg = mean_{j->i} x[j]   K1 (gnn_sage_mean_fwd_planes), once per
+                                                           registered x and graph plan
     columns [col2, col2 + k2)     x                        written once per input tensor
     everything else               zero
 
 ``x`` is a constant of the training run (the reference prepares it once, src/train_gnn.py:
 315-350), so its planes are cached on the tensor like the graph plan (graph.py), keyed on
-(data_ptr, _version): an in-place edit of x rebuilds them.  The agg half is recomputed on every
-forward — nothing computed from the weights or the step's inputs is reused across steps.
+(data_ptr, _version): an in-place edit of x rebuilds them.
 
-A forward stamps the image with a generation number; the backward checks it, and recomputes
-the agg half (deterministically: the same bits) if another grad-enabled forward over the same x
-ran in between.
+The agg half depends on x and the graph plan alone — not on the weights, the dropout seed or the
+step — and K1 is deterministic, so for a registered x it is cached too (``mean_cached``): K1 runs
+when the image's agg half does not already hold the means of this (x, plan, hub form, exp), which
+in a training run is the first forward; every later epoch and evaluation over the same edge_index
+reads the same bits K1 would write again.  Nothing computed from the weights or the step's inputs
+is reused across steps.  GNNMP_AGG_CACHE=0 (fused.py) runs K1 on every forward.  The rules that
+keep the cache right under graph capture are ``mean_cached``'s (``_AggCache``); the bf16-storage
+layer-0 image (``BfImage``, ``bf_x_image``) caches its aggregate the same way.
+
+A forward stamps the image with a generation number (bumped by every K1 run); the backward
+checks it, and recomputes the agg half (deterministically: the same bits) if a forward over
+another plan rewrote it in between.
 """
 from __future__ import annotations
 
 import ctypes
+import weakref
 
 import torch
 
@@ -34,7 +43,72 @@ def _pad8(k: int) -> int:
     return (k + 7) // 8 * 8
 
 
-class SplitImage:
+def _capturing() -> bool:
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class _AggCache:
+    """The agg half of a layer-0 image as a cache (module docstring): what it holds, and the
+    rules that keep that right under graph capture."""
+
+    def _agg_init(self) -> None:
+        self.agg_key = None        # what the agg half holds (mean_cached), None: unknown
+        self.agg_pin = None        # the key a captured step that skipped the gather reads on every replay
+        self.agg_volatile = False  # a gather was captured: replays rewrite the agg half unseen
+        self._agg_event = None     # (stream, event) of the gather agg_key records
+
+    def agg_key_of(self, plan, hub=True):
+        """The identity of an agg half: x's image key, the plan object (plans are rebuilt when
+        edge_index is edited, so identity suffices; held weakly), the hub choice and exp."""
+        return (self.x_key, weakref.ref(plan), bool(hub), int(getattr(self, "exp", 0)))
+
+    @staticmethod
+    def _same_key(a, b) -> bool:
+        if a is None or b is None:
+            return False
+        pa, pb = a[1](), b[1]()
+        return pa is not None and pa is pb and a[0] == b[0] and a[2:] == b[2:]
+
+    def agg_foreign(self, plan, hub=True) -> bool:
+        """Whether a captured step pinned the agg half to another key than (plan, hub)'s: a gather
+        for this plan would overwrite what that step's replays read."""
+        return self.agg_pin is not None and not self._same_key(self.agg_pin, self.agg_key_of(plan, hub))
+
+    def agg_reset(self) -> None:
+        """x was edited (its planes are rebuilt): the agg half is stale and no longer pinned."""
+        self.agg_key = None
+        self.agg_pin = None
+
+    def _agg_written(self) -> None:
+        """Before any launch that writes the agg half."""
+        self.agg_key = None  # rewritten: recorded again after the launch (_agg_record)
+        if _capturing():
+            self.agg_volatile = True
+
+    def _agg_hit(self, key, x: torch.Tensor, cache=True) -> bool:
+        if not (cache and not self.agg_volatile and is_registered(x) and self._same_key(self.agg_key, key)):
+            return False
+        if _capturing():
+            self.agg_pin = key
+        elif self._agg_event is not None:
+            st, ev = self._agg_event
+            cur = torch.cuda.current_stream(x.device)
+            if st != cur:  # the gather ran on another stream
+                cur.wait_event(ev)
+        return True
+
+    def _agg_record(self, key, x: torch.Tensor, cache=True) -> None:
+        if cache and not _capturing() and not self.agg_volatile and is_registered(x):
+            self.agg_key = key
+            self._agg_event = None
+            if x.is_cuda:
+                cur = torch.cuda.current_stream(x.device)
+                ev = torch.cuda.Event()
+                ev.record(cur)
+                self._agg_event = (cur, ev)
+
+
+class SplitImage(_AggCache):
     """[3, N, ld] bf16 planes of [A1 | A2] with A1 at column 0 and A2 at column ``col2``."""
 
     nplanes = 3
@@ -64,6 +138,7 @@ class SplitImage:
         self.gen = 0
         self.x_key = None
         self.exp = 0  # half-pair images: the pre-scale exponent of the image's values (h2_exp)
+        self._agg_init()
 
     @property
     def ptr(self) -> int:
@@ -90,6 +165,7 @@ class SplitImage:
         hub rows on blocks of their own); False: one wave per 16 rows throughout."""
         from .aggregation import KernelTimer, agg_bytes
 
+        self._agg_written()
         e0 = KernelTimer.begin()
         src, F = (x_pad, int(x_pad.size(1))) if x_pad is not None else (x, self.k1)
         args = (plan.c_graph, plan.deg.data_ptr(), src.data_ptr(), int(src.stride(0)), F, self.ptr, self.ld,
@@ -107,6 +183,26 @@ class SplitImage:
         self.gen += 1
         return self.gen
 
+    def mean_cached(self, plan, x: torch.Tensor, keep=None, prep_b=None, x_pad=None, hub=True, cache=True):
+        """The agg half for (x, plan): (generation, hit).  A hit launches nothing — the image
+        already holds these means — and needs: the same key as the last K1 recorded
+        (agg_key_of), a registered x, no keep bits asked of K1, ``cache`` (GNNMP_AGG_CACHE).
+        Otherwise K1 runs (fill_mean; ``prep_b`` may be a callable, evaluated only then) and
+        its key is recorded.
+
+        Under stream capture: a key is never recorded (a captured K1 has not run), and an image
+        whose K1 was captured stays uncached, since every replay rewrites its agg half.  A
+        captured step that hit the cache pins the image to its key: its replays read the agg
+        half, so no K1 for another key may write it (agg_foreign; fused._layer0_image then takes
+        the f32-operand path) until x is edited."""
+        key = self.agg_key_of(plan, hub)
+        if keep is None and self._agg_hit(key, x, cache):
+            return self.gen, True
+        if callable(prep_b):
+            prep_b = prep_b()
+        gen = self.fill_mean(plan, x, keep, prep_b=prep_b, x_pad=x_pad, hub=hub)
+        self._agg_record(key, x, cache)
+        return gen, False
 
 class HalfPairImage(SplitImage):
     """[2, N, ld] f16 half-pair planes of [A1 | A2] · 2^exp (include/gnnmp.h gnn_split_h2_f32):
@@ -166,6 +262,7 @@ def x_image(x: torch.Tensor, cls=SplitImage) -> SplitImage:
     if im.x_key != key:
         im.fill_x(x)
         im.x_key = key
+        im.agg_reset()
     return im
 
 
@@ -236,7 +333,8 @@ def register_input(x: torch.Tensor) -> torch.Tensor:
     """Declare x a constant input of the run (the training loop's node features, prepared once,
     src/train_gnn.py:315-350): layers whose A operand is x then read it from a split image built
     once per (unmodified) x — a per-graph input layout, like the CSR plan: the SAGE layer-1
-    [agg | x] image (x half) and the GCN / GAT layer-1 x-only image.  Unregistered inputs (a
+    [agg | x] image (the x half once per x, the agg half once per x and graph plan:
+    SplitImage.mean_cached) and the GCN / GAT layer-1 x-only image.  Unregistered inputs (a
     mini-batch's gathered rows, a per-step time-injected input) keep the f32-operand kernels, so
     no call allocates an image or pays a split pass it cannot reuse.  Returns x."""
     try:
@@ -285,7 +383,7 @@ def x_only_image(x: torch.Tensor, cls=SplitImage):
 
 
 # ----------------------------------------------------------------------------- bf16 images
-class BfImage:
+class BfImage(_AggCache):
     """One-plane bf16 image [N, ld] of a bf16-storage layer operand [A1 | A2] (BASELINE configs[4]):
     A1 (the layer's aggregate) in columns [0, k1), A2 (its input h) in [col2, col2 + k2), zeros
     elsewhere, ld a multiple of 16 (whole MFMA k-steps).  The producers write straight into it —
@@ -303,6 +401,18 @@ class BfImage:
         alloc = torch.zeros if (zero or self.col2 != self.k1 or self.col2 + self.k2 != self.ld) else torch.empty
         self.img = alloc((self.n, self.ld), dtype=torch.bfloat16, device=device)
         self.x_key = None
+        self._agg_init()
+
+    def mean_cached(self, plan, x: torch.Tensor, fill, cache=True) -> bool:
+        """The layer-0 agg half for (x, plan), as SplitImage.mean_cached: ``fill()`` (the bf16
+        aggregation into ``a1``) runs unless the image already holds it; returns whether it did."""
+        key = self.agg_key_of(plan)
+        if self._agg_hit(key, x, cache):
+            return True
+        self._agg_written()
+        fill()
+        self._agg_record(key, x, cache)
+        return False
 
     @property
     def ptr(self) -> int:
@@ -319,7 +429,8 @@ class BfImage:
 
 def bf_x_image(x: torch.Tensor) -> BfImage:
     """The cached bf16 image of [agg | x] for a bf16 input x (its x half copied in once, like the
-    graph plan: rebuilt after an in-place edit of x); the agg half is rewritten every forward."""
+    graph plan: rebuilt after an in-place edit of x); the agg half is written once per registered
+    x and plan (BfImage.mean_cached)."""
     key = (x.data_ptr(), x._version, tuple(x.shape), tuple(x.stride()))
     attr = _ATTR + "_bf16"
     im = getattr(x, attr, None)
@@ -332,4 +443,5 @@ def bf_x_image(x: torch.Tensor) -> BfImage:
     if im.x_key != key:
         im.a2.copy_(x)  # one layout copy per input tensor (the padding columns stay zero)
         im.x_key = key
+        im.agg_reset()
     return im
