@@ -545,7 +545,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TNArgs a) {
       int64_t m = m0 + rg * GR + i;
       m = m < mend ? m : mend - 1;  // clamped: always a valid row, masked in store_chunk
       if constexpr (PROJ) {
-        if (a.nproj == 4 && (a.lddz & 3) == 0) {
+        if (a.nproj == 4 && (a.lddz & 3) == 0 && (reinterpret_cast<uintptr_t>(a.dz) & 15) == 0) {
           float4 t = *reinterpret_cast<const float4*>(a.dz + m * a.lddz);
           rg_in[i][0] = t.x; rg_in[i][1] = t.y; rg_in[i][2] = t.z; rg_in[i][3] = t.w;
         } else {

@@ -30,7 +30,7 @@ import torch
 from . import _lib
 from .aggregation import KernelTimer, aggregate, agg_bytes
 from .graph import GraphPlan, get_plan
-from .planes import (BfImage, HalfPairImage, SplitImage, bf_x_image, h2_ok, is_registered, mean_planes_ok, x_padded,
+from .planes import (BfImage, HalfPairImage, SplitImage, bf_x_image, h2_ok, is_registered, mean_planes_ok, padded_mean_planes_ok, x_padded,
                      register_input, x_image, x_only_image)
 
 # The layer-1 operand [agg | x] as a split image (planes.py): on by default, GNNMP_PLANES=0 runs
@@ -370,6 +370,12 @@ def gemm_tn_input(nr: int, x: torch.Tensor, g: torch.Tensor):
     return gemm_tn(nr, x, g=g)
 
 
+def _k1_pads(x: torch.Tensor) -> bool:
+    """Whether layer 0's K1 gathers planes.x_padded(x) (GNNMP_K1_PAD, and x narrower than the
+    image's agg half of pad8(F) columns) instead of x itself."""
+    return _K1_PAD and (x.size(1) + 7) // 8 * 8 > x.size(1)
+
+
 def _layer0_image(x: torch.Tensor, n_out: int, nt_kw, h2: bool = False, plan=None):
     """The split image of [agg | x] when the planes path takes this layer (else None): x must be a
     registered constant input (planes.register_input) — its planes are built once and reused; a
@@ -380,6 +386,8 @@ def _layer0_image(x: torch.Tensor, n_out: int, nt_kw, h2: bool = False, plan=Non
     as another plan's means on every replay (SplitImage.agg_foreign): this forward must not
     overwrite it."""
     if not (_PLANES and is_registered(x) and mean_planes_ok(x)) or x.size(0) < 32:
+        return None
+    if _k1_pads(x) and not padded_mean_planes_ok(x):  # K1 must take the padded copy the forward gathers
         return None
     if h2 and _H2 and HalfPairImage.addressable(x.size(0), x.size(1), x.size(1)) and h2_ok(x):
         im = x_image(x, HalfPairImage)
@@ -485,7 +493,7 @@ class _FusedSAGE(torch.autograd.Function):
                     with torch.cuda.stream(side):
                         gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="prep", **nt_kw)
                     ready = True
-                xp = x_padded(h, im.col2) if _K1_PAD and im.col2 % 4 == 0 and im.col2 > h.size(1) else None
+                xp = x_padded(h, im.col2) if _k1_pads(h) else None
                 gen, hit = im.mean_cached(plan, h, keep, prep_b=prep_b, x_pad=xp, cache=_AGG_CACHE)
                 ctx.image = (im, gen)
                 if side is not None:

@@ -238,13 +238,32 @@ class HalfPairImage(SplitImage):
 H2_TOP = 14  # a half-pair image's largest magnitude is pre-scaled into [2^(H2_TOP-1), 2^H2_TOP)
 
 
+def _k1_takes(ptr: int, ldx: int, F: int, width: int) -> bool:
+    """The predicate of gnn_sage_mean_fwd_planes / _h2 (aggregate.hip sage_mean_fwd_image) for a
+    gather source at ``ptr`` with pitch ``ldx`` and an image whose agg half is ``width`` wide: the
+    images themselves are allocator-aligned with ld and plane stride multiples of 16."""
+    v4 = F % 4 == 0 and ldx % 4 == 0 and width % 4 == 0 and ptr % 16 == 0
+    v2 = F % 2 == 0 and ldx % 2 == 0 and width % 2 == 0 and ptr % 8 == 0
+    vec = 4 if v4 else 2
+    return v2 and F // vec > 32 and -(-width // vec) <= 128
+
+
 def mean_planes_ok(x: torch.Tensor) -> bool:
-    """Whether gnn_sage_mean_fwd_planes takes x (f32 rows, even F with 32 < F/vec, F <= 256)."""
+    """Whether gnn_sage_mean_fwd_planes / _h2 takes x itself as its gather source (f32 rows, even F
+    with 32 < F/vec, the image's agg half at most 128 lane pieces wide, x 8-byte aligned — 16 for
+    the 4-wide gather).  A forward that gathers x_padded(x) instead asks padded_mean_planes_ok
+    too; x itself is still asked there, since a backward that refills the agg half
+    (SplitImage.fill_mean without x_pad) gathers x."""
     if x.dtype != torch.float32 or x.dim() != 2 or x.stride(1) != 1 or not x.is_cuda:
         return False
-    F = x.size(1)
-    vec = 4 if (F % 4 == 0 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0) else 2
-    return F % 2 == 0 and x.stride(0) % 2 == 0 and F // vec > 32 and _pad8(F) // vec <= 128
+    return _k1_takes(x.data_ptr(), x.stride(0), x.size(1), _pad8(x.size(1)))
+
+
+def padded_mean_planes_ok(x: torch.Tensor) -> bool:
+    """Whether K1 takes x_padded(x, pad8(F)) (its own 16-byte rows, as wide as the image's agg
+    half): e.g. F = 70 pads to 72 columns, 18 lane pieces of 4 — fewer than K1's 32."""
+    col2 = _pad8(x.size(1))
+    return _k1_takes(0, col2, col2, col2)
 
 
 def x_image(x: torch.Tensor, cls=SplitImage) -> SplitImage:
