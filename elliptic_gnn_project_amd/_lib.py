@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -199,6 +199,15 @@ class GnnAdamGroup(ctypes.Structure):
     ]
 
 
+class GnnCeSpec(ctypes.Structure):
+    """gnn_ce_spec (ABI 27): the masked CE's operands and loss variant, shared by every _spec entry."""
+    _fields_ = [
+        ("y", c_ptr), ("mask", c_ptr), ("class_w", c_ptr), ("row_w", c_ptr),
+        ("inv_denom", ctypes.c_float), ("focal", c_i32), ("focal_gamma", ctypes.c_float),
+        ("reserved", c_i32 * 5),
+    ]
+
+
 # name -> (restype, argtypes).  Mirrors include/gnnmp.h one to one; the CPU test
 # suite checks that every function declared in the header appears here and is exported.
 SIGNATURES = {
@@ -324,6 +333,24 @@ SIGNATURES = {
         [c_i64, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr,
          c_ptr],
     ),
+    "gnn_masked_ce_spec_f32": (
+        ctypes.c_int,
+        [c_i64, c_i32, c_ptr, c_i64, ctypes.POINTER(GnnCeSpec), c_ptr, c_i64, c_ptr, c_ptr, c_size, c_ptr, c_ptr],
+    ),
+    "gnn_sage_out_mean_ce_spec_f32": (
+        ctypes.c_int,
+        [ctypes.POINTER(GnnGraph), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i64, ctypes.POINTER(GnnCeSpec),
+         c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr],
+    ),
+    "gnn_gcn_out_ce_spec_f32": (
+        ctypes.c_int,
+        [ctypes.POINTER(GnnGraph), c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i64, ctypes.POINTER(GnnCeSpec),
+         c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr],
+    ),
+    "gnn_gat_out_ce_spec_f32": (
+        ctypes.c_int,
+        [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnGatFwdParams), ctypes.POINTER(GnnCeSpec), c_ptr, c_i64,
+         c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_clip_adam_workspace_size": (ctypes.c_int, [ctypes.POINTER(c_size)]),
     "gnn_neighbor_sample_workspace_size": (ctypes.c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_size)]),
     "gnn_neighbor_sample": (

@@ -139,6 +139,7 @@ struct AggArgs {
   const int64_t* ce_y; const uint8_t* ce_mask; const float* ce_w; float ce_inv;
   float* ce_dl; int64_t ce_ldd; float* ce_part;
   float* ce_u; int64_t ce_ldu;  // optional: dl / max(deg, 1) per row (the transposed mean's per-slot term)
+  const float* ce_rw; int32_t ce_focal; float ce_gamma;  // CEV (gnn_ce_spec): per-row weights (optional), focal, its gamma
   float* ce_cs;                 // optional: per-256-row-block column sums of dl, [block][C] (the bias gradient)
 };
 
@@ -963,7 +964,9 @@ __global__ __launch_bounds__(256) void agg_group_kernel(AggArgs a) {
 // epilogue (masked_ce_kernel's arithmetic, bit for bit: a block's 4 waves x 64 rows are that
 // kernel's 256-row block, its loss partial summed in the same order); waves past the last row
 // then stay for the block's one barrier instead of returning.
-template <int MODE, int NF, int kNarrowCap = 256, bool COOP = false, bool CE = false>  // kNarrowCap: slots staged per pass per wave
+// CEV: the CE of a gnn_ce_spec with row weights or focal (masked_ce_row<4, true>); the plain CE
+// instantiations are untouched by it.
+template <int MODE, int NF, int kNarrowCap = 256, bool COOP = false, bool CE = false, bool CEV = false>  // kNarrowCap: slots staged per pass per wave
 __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
   __shared__ float sv[4][kNarrowCap * 4];
   const int lane = threadIdx.x & 63;
@@ -974,6 +977,7 @@ __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
   float ce_deg = 1.0f;                 // CE: max(deg, 1) of the row (the u output's divisor)
   uint8_t ce_m = 0;
   float ce_w[4] = {0.f, 0.f, 0.f, 0.f};
+  float ce_rw = 1.0f;                  // CEV: the row's weight
   if constexpr (!CE) {
     if (r0 >= a.nrows) return;  // wave-uniform; no block barriers below
   }
@@ -1016,6 +1020,9 @@ __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
     ce_m = a.ce_mask[rr];
 #pragma unroll
     for (int c = 0; c < 4; ++c) ce_w[c] = a.ce_w[c < F ? c : 0];
+    if constexpr (CEV) {
+      if (a.ce_rw) ce_rw = a.ce_rw[rr];
+    }
   }
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   float* buf = sv[w];
@@ -1131,7 +1138,11 @@ __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
       const int64_t tg = ce_t;
       const bool on = ce_m != 0 && tg >= 0 && tg < C;
       const float wt = tg == 0 ? ce_w[0] : tg == 1 ? ce_w[1] : tg == 2 ? ce_w[2] : ce_w[3];
-      l = masked_ce_row<4>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv);
+      if constexpr (CEV)
+        l = masked_ce_row<4, true>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv, ce_rw,
+                                   a.ce_focal != 0, a.ce_gamma);
+      else
+        l = masked_ce_row<4>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv);
       if (a.ce_u) {  // MEAN_BWD's v / max(deg, 1) of this row, the same division (deg is MEAN's nodew)
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -1819,17 +1830,33 @@ extern "C" gnn_status gnn_sage_mean_fwd_h2(const gnn_graph* g, const float* deg,
 extern "C" gnn_status gnn_masked_ce_finish(const float* partial, int32_t nblk, float inv_denom, float* loss,
                                            gnn_stream_t stream);
 
-extern "C" gnn_status gnn_sage_out_mean_ce_f32(const gnn_graph* g, const float* deg, const float* z, int64_t ldz,
-                                               int32_t C, const float* bias, float* logits, int64_t ldo,
-                                               const int64_t* y, const uint8_t* mask, const float* class_w,
-                                               float inv_denom, float* dlogits, int64_t ld_d, float* u, int64_t ldu,
-                                               float* colsum, float* loss, void* workspace, size_t workspace_bytes,
-                                               gnn_stream_t stream) {
-  const char* fn = __func__;
+static gnn_status ce_spec_check(const gnn_ce_spec* sp, const char* fn) {
+  if (!sp) return fail(GNN_ERR_INVALID_ARG, fn, "null spec");
+  if (sp->focal && !(sp->focal_gamma >= 1.0f))
+    return fail(GNN_ERR_INVALID_ARG, fn, "focal_gamma < 1 (unbounded gradient at p = 1)");
+  return GNN_OK;
+}
+
+static gnn_ce_spec plain_spec(const int64_t* y, const uint8_t* mask, const float* class_w, float inv_denom) {
+  gnn_ce_spec sp{};
+  sp.y = y; sp.mask = mask; sp.class_w = class_w; sp.inv_denom = inv_denom;
+  return sp;
+}
+
+static void ce_args(AggArgs& a, const gnn_ce_spec& sp, float* dlogits, int64_t ld_d, float* partial, float* colsum) {
+  a.ce_y = sp.y; a.ce_mask = sp.mask; a.ce_w = sp.class_w; a.ce_inv = sp.inv_denom; a.ce_dl = dlogits; a.ce_ldd = ld_d;
+  a.ce_part = partial; a.ce_cs = colsum;
+  a.ce_rw = sp.row_w; a.ce_focal = sp.focal; a.ce_gamma = sp.focal_gamma;
+}
+
+static gnn_status sage_out_mean_ce(const char* fn, const gnn_graph* g, const float* deg, const float* z, int64_t ldz,
+                                   int32_t C, const float* bias, float* logits, int64_t ldo, const gnn_ce_spec& sp,
+                                   float* dlogits, int64_t ld_d, float* u, int64_t ldu, float* colsum, float* loss,
+                                   void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
   if (!g || !deg) return fail(GNN_ERR_INVALID_ARG, fn, "null graph or deg");
   if (C < 1 || C > 4 || ldz < 2 * C || ldo < C || ld_d < C) return fail(GNN_ERR_INVALID_ARG, fn, "needs 1 <= C <= 4, ldz >= 2C");
   const int64_t N = g->num_nodes;
-  if (N > 0 && (!z || !logits || !y || !mask || !class_w || !dlogits)) return fail(GNN_ERR_INVALID_ARG, fn, "null operand");
+  if (N > 0 && (!z || !logits || !sp.y || !sp.mask || !sp.class_w || !dlogits)) return fail(GNN_ERR_INVALID_ARG, fn, "null operand");
   if (!g->rowptr || (g->num_slots > 0 && !g->col)) return fail(GNN_ERR_INVALID_ARG, fn, "plan arrays null");
   const int nblk = (int)std::max<int64_t>(1, ceil_div(N, 256));
   if (!workspace || workspace_bytes < (size_t)nblk * sizeof(float)) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
@@ -1844,28 +1871,47 @@ extern "C" gnn_status gnn_sage_out_mean_ce_f32(const gnn_graph* g, const float* 
   a.x = z; a.ldx = ldz; a.y = logits; a.ldy = ldo;
   a.add = z + C; a.ld_add = ldz; a.bias = bias;
   a.nrows = N; a.F = C;
-  a.ce_y = y; a.ce_mask = mask; a.ce_w = class_w; a.ce_inv = inv_denom; a.ce_dl = dlogits; a.ce_ldd = ld_d;
-  a.ce_part = partial;
+  ce_args(a, sp, dlogits, ld_d, partial, colsum);
   if (u && ldu < C) return fail(GNN_ERR_INVALID_ARG, fn, "ldu < C");
   a.ce_u = u; a.ce_ldu = ldu;
-  a.ce_cs = colsum;
-  if (C <= 2) agg_narrow_lds_kernel<GNN_AGG_MEAN, 2, 256, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  const bool var = sp.row_w || sp.focal;
+  if (var && C <= 2) agg_narrow_lds_kernel<GNN_AGG_MEAN, 2, 256, true, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  else if (var) agg_narrow_lds_kernel<GNN_AGG_MEAN, 4, 256, true, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  else if (C <= 2) agg_narrow_lds_kernel<GNN_AGG_MEAN, 2, 256, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
   else agg_narrow_lds_kernel<GNN_AGG_MEAN, 4, 256, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
   const gnn_status s = hip_check(hipGetLastError(), fn);
   if (s != GNN_OK || !loss) return s;  // loss NULL: the partials stay in the workspace (ClipAdam / finish)
-  return gnn_masked_ce_finish(partial, nblk, inv_denom, loss, stream);
+  return gnn_masked_ce_finish(partial, nblk, sp.inv_denom, loss, stream);
 }
 
-extern "C" gnn_status gnn_gcn_out_ce_f32(const gnn_graph* g, const float* dinv, const float* t, int64_t ldt,
-                                         int32_t C, const float* bias, float* logits, int64_t ldo,
-                                         const int64_t* y, const uint8_t* mask, const float* class_w,
-                                         float inv_denom, float* dlogits, int64_t ld_d, float* colsum, float* loss,
-                                         void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
-  const char* fn = __func__;
+extern "C" gnn_status gnn_sage_out_mean_ce_f32(const gnn_graph* g, const float* deg, const float* z, int64_t ldz,
+                                               int32_t C, const float* bias, float* logits, int64_t ldo,
+                                               const int64_t* y, const uint8_t* mask, const float* class_w,
+                                               float inv_denom, float* dlogits, int64_t ld_d, float* u, int64_t ldu,
+                                               float* colsum, float* loss, void* workspace, size_t workspace_bytes,
+                                               gnn_stream_t stream) {
+  return sage_out_mean_ce(__func__, g, deg, z, ldz, C, bias, logits, ldo, plain_spec(y, mask, class_w, inv_denom),
+                          dlogits, ld_d, u, ldu, colsum, loss, workspace, workspace_bytes, stream);
+}
+
+extern "C" gnn_status gnn_sage_out_mean_ce_spec_f32(const gnn_graph* g, const float* deg, const float* z, int64_t ldz,
+                                                    int32_t C, const float* bias, float* logits, int64_t ldo,
+                                                    const gnn_ce_spec* spec, float* dlogits, int64_t ld_d, float* u,
+                                                    int64_t ldu, float* colsum, float* loss, void* workspace,
+                                                    size_t workspace_bytes, gnn_stream_t stream) {
+  if (const gnn_status s = ce_spec_check(spec, __func__); s != GNN_OK) return s;
+  return sage_out_mean_ce(__func__, g, deg, z, ldz, C, bias, logits, ldo, *spec, dlogits, ld_d, u, ldu, colsum, loss,
+                          workspace, workspace_bytes, stream);
+}
+
+static gnn_status gcn_out_ce(const char* fn, const gnn_graph* g, const float* dinv, const float* t, int64_t ldt,
+                             int32_t C, const float* bias, float* logits, int64_t ldo, const gnn_ce_spec& sp,
+                             float* dlogits, int64_t ld_d, float* colsum, float* loss, void* workspace,
+                             size_t workspace_bytes, gnn_stream_t stream) {
   if (!g || !dinv) return fail(GNN_ERR_INVALID_ARG, fn, "null graph or dinv");
   if (C < 1 || C > 2 || ldt < C || ldo < C || ld_d < C) return fail(GNN_ERR_INVALID_ARG, fn, "needs 1 <= C <= 2");
   const int64_t N = g->num_nodes;
-  if (N < 1 || !t || !logits || !y || !mask || !class_w || !dlogits) return fail(GNN_ERR_INVALID_ARG, fn, "null operand / N < 1");
+  if (N < 1 || !t || !logits || !sp.y || !sp.mask || !sp.class_w || !dlogits) return fail(GNN_ERR_INVALID_ARG, fn, "null operand / N < 1");
   if (!g->rowptr || (g->num_slots > 0 && !g->col)) return fail(GNN_ERR_INVALID_ARG, fn, "plan arrays null");
   const int nblk = (int)ceil_div(N, 256);
   if (!workspace || workspace_bytes < (size_t)nblk * sizeof(float)) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
@@ -1875,12 +1921,31 @@ extern "C" gnn_status gnn_gcn_out_ce_f32(const gnn_graph* g, const float* dinv, 
   a.ptr = g->rowptr; a.nbr = g->col; a.nodew = dinv; a.heads = 1; a.chan = C;
   a.x = t; a.ldx = ldt; a.y = logits; a.ldy = ldo; a.bias = bias;
   a.nrows = N; a.F = C;
-  a.ce_y = y; a.ce_mask = mask; a.ce_w = class_w; a.ce_inv = inv_denom; a.ce_dl = dlogits; a.ce_ldd = ld_d;
-  a.ce_part = partial; a.ce_cs = colsum;
-  agg_narrow_lds_kernel<GNN_AGG_GCN, 2, 256, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  ce_args(a, sp, dlogits, ld_d, partial, colsum);
+  if (sp.row_w || sp.focal) agg_narrow_lds_kernel<GNN_AGG_GCN, 2, 256, true, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  else agg_narrow_lds_kernel<GNN_AGG_GCN, 2, 256, true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
   const gnn_status s = hip_check(hipGetLastError(), fn);
   if (s != GNN_OK || !loss) return s;
-  return gnn_masked_ce_finish(partial, nblk, inv_denom, loss, stream);
+  return gnn_masked_ce_finish(partial, nblk, sp.inv_denom, loss, stream);
+}
+
+extern "C" gnn_status gnn_gcn_out_ce_f32(const gnn_graph* g, const float* dinv, const float* t, int64_t ldt,
+                                         int32_t C, const float* bias, float* logits, int64_t ldo,
+                                         const int64_t* y, const uint8_t* mask, const float* class_w,
+                                         float inv_denom, float* dlogits, int64_t ld_d, float* colsum, float* loss,
+                                         void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
+  return gcn_out_ce(__func__, g, dinv, t, ldt, C, bias, logits, ldo, plain_spec(y, mask, class_w, inv_denom), dlogits,
+                    ld_d, colsum, loss, workspace, workspace_bytes, stream);
+}
+
+extern "C" gnn_status gnn_gcn_out_ce_spec_f32(const gnn_graph* g, const float* dinv, const float* t, int64_t ldt,
+                                              int32_t C, const float* bias, float* logits, int64_t ldo,
+                                              const gnn_ce_spec* spec, float* dlogits, int64_t ld_d, float* colsum,
+                                              float* loss, void* workspace, size_t workspace_bytes,
+                                              gnn_stream_t stream) {
+  if (const gnn_status s = ce_spec_check(spec, __func__); s != GNN_OK) return s;
+  return gcn_out_ce(__func__, g, dinv, t, ldt, C, bias, logits, ldo, *spec, dlogits, ld_d, colsum, loss, workspace,
+                    workspace_bytes, stream);
 }
 
 extern "C" gnn_status gnn_sage_mean_bwd_f32(const gnn_graph* g, const float* deg, const float* dout,

@@ -108,28 +108,70 @@ __device__ __forceinline__ float ce_logf(float x) {
   return v - (tiny ? __uint_as_float(0x41b17218u) : 0.f);  // 32·ln2
 }
 
-template <int CM>
+// VAR (gnn_ce_spec's variants; the plain instantiation is the code it was): ``rw`` the row's weight
+// (loss and gradient times rw) and, with ``focal``, loss = -(1 - p)^γ·log p (no class weight) and
+// dl = rw·inv·k·(softmax - onehot), k = (1 - p)^γ - γ·(1 - p)^(γ-1)·p·log p, p the target's softmax
+// probability.  1 - p is the other classes' exponentials over their sum (never 1.0f - p: relative
+// accuracy as p -> 1); γ = 1 and 2 are products ((1 - p)^0 = 1 also at p = 1), any other γ >= 1
+// goes through ce_expf(γ·ce_logf(1 - p)) with (1 - p) = 0 -> 0.  The target's softmax - 1 is that
+// -(1 - p) too.
+template <int CM, bool VAR = false>
 __device__ __forceinline__ float masked_ce_row(float (&v)[CM], int C, int64_t t, bool on, float wt, float inv,
-                                               float* __restrict__ dl, float* dlv = nullptr) {
+                                               float* __restrict__ dl, float* dlv = nullptr, float rw = 1.0f,
+                                               bool focal = false, float gamma = 0.f) {
 #pragma clang fp contract(off)
   float mx = -INFINITY;
 #pragma unroll
   for (int c = 0; c < CM; ++c)
     if (c < C) mx = fmaxf(mx, v[c]);
   float s = 0.f, xt = 0.f;
+  float et = 0.f, so = 0.f;  // VAR: the target's exponential and the sum of the others
 #pragma unroll
   for (int c = 0; c < CM; ++c)
     if (c < C) {
       if (c == t) xt = v[c];
       v[c] = ce_expf(v[c] - mx);
       s += v[c];
+      if constexpr (VAR) {
+        if (c == t) et = v[c];
+        else so += v[c];
+      }
     }
-  const float l = on ? -wt * (xt - mx - ce_logf(s)) : 0.f;
-  const float g = wt * inv, rs = 1.0f / s;
+  float l, g, om = 0.f;  // (VAR: om = 1 - p)
+  const float rs = 1.0f / s;
+  if constexpr (!VAR) {
+    l = on ? -wt * (xt - mx - ce_logf(s)) : 0.f;
+    g = wt * inv;
+  } else {
+    const float lp = xt - mx - ce_logf(s);
+    float base = -wt * lp, k = wt;
+    om = so * rs;
+    if (focal) {
+      const float p = et * rs;
+      float pg, pg1;  // (1 - p)^γ, (1 - p)^(γ-1)
+      if (gamma == 1.0f) {
+        pg = om;
+        pg1 = 1.0f;
+      } else if (gamma == 2.0f) {
+        pg = om * om;
+        pg1 = om;
+      } else {
+        const float lo = ce_logf(om);
+        pg = om > 0.f ? ce_expf(gamma * lo) : 0.f;
+        pg1 = om > 0.f ? ce_expf((gamma - 1.0f) * lo) : 0.f;
+      }
+      base = -pg * lp;
+      k = pg - ((gamma * pg1) * p) * lp;
+    }
+    l = on ? rw * base : 0.f;
+    g = rw * (k * inv);
+  }
 #pragma unroll
   for (int c = 0; c < CM; ++c)
     if (c < C) {
-      const float d = on ? g * fmaf(v[c], rs, c == t ? -1.f : 0.f) : 0.f;
+      float sm = fmaf(v[c], rs, c == t ? -1.f : 0.f);  // softmax - onehot
+      if constexpr (VAR) sm = c == t ? -om : sm;       // (the target's p - 1 without the cancellation)
+      const float d = on ? g * sm : 0.f;
       dl[c] = d;
       if (dlv) dlv[c] = d;  // (the caller's copy: aggregate.hip's per-row term of the transposed mean)
     }

@@ -1181,8 +1181,9 @@ struct GatOutArgs {
   float* out; int64_t ldo;
   const int64_t* ce_y; const uint8_t* ce_mask; const float* ce_w; float ce_inv;
   float* ce_dl; int64_t ce_ldd; float* ce_part; float* ce_cs;
+  const float* ce_rw; int32_t ce_focal; float ce_gamma;  // CEV (gnn_ce_spec): per-row weights (optional), focal, its gamma
 };
-template <bool CE>
+template <bool CE, bool CEV = false>  // CEV: the CE of a spec with row weights or focal (masked_ce_row<4, true>)
 __global__ __launch_bounds__(256) void gat_out_narrow_kernel(GatOutArgs a) {
   // no implicit FMA contraction: the CE and no-CE instances (and the window sizes) must round the
   // softmax sums identically (tests: the fused-CE step bit-identical to the separate one)
@@ -1199,6 +1200,7 @@ __global__ __launch_bounds__(256) void gat_out_narrow_kernel(GatOutArgs a) {
   int64_t ce_t = -1;
   uint8_t ce_m = 0;
   float ce_w[2] = {0.f, 0.f};
+  float ce_rw = 1.0f;
   if constexpr (!CE) {
     if (r0 >= a.N) return;  // wave-uniform; no block barrier below
   }
@@ -1221,6 +1223,9 @@ __global__ __launch_bounds__(256) void gat_out_narrow_kernel(GatOutArgs a) {
       ce_m = a.ce_mask[rr];
       ce_w[0] = a.ce_w[0];
       ce_w[1] = a.ce_w[C > 1 ? 1 : 0];
+      if constexpr (CEV) {
+        if (a.ce_rw) ce_rw = a.ce_rw[rr];
+      }
     }
     const float adr = C > 1 ? xi0 * ad0 + xi1 * ad1 : xi0 * ad0;  // (xh_i * att_dst).sum(-1)
     const float asr = C > 1 ? xi0 * as0 + xi1 * as1 : xi0 * as0;
@@ -1372,7 +1377,11 @@ __global__ __launch_bounds__(256) void gat_out_narrow_kernel(GatOutArgs a) {
       const int64_t tg = ce_t;
       const bool on = ce_m != 0 && tg >= 0 && tg < C;
       const float wt = tg == 0 ? ce_w[0] : ce_w[1];
-      l = masked_ce_row<4>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv);
+      if constexpr (CEV)
+        l = masked_ce_row<4, true>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv, ce_rw,
+                                   a.ce_focal != 0, a.ce_gamma);
+      else
+        l = masked_ce_row<4>(lg, C, tg, on, on ? wt : 0.f, a.ce_inv, a.ce_dl + r * a.ce_ldd, dlv);
     }
     __shared__ float cesh[4];
     for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o);  // train_ops.hip block_sum, same order
@@ -1825,11 +1834,9 @@ extern "C" gnn_status gnn_gat_bwd_ew_f32(const gnn_graph* g, int32_t H, int32_t 
 extern "C" gnn_status gnn_masked_ce_finish(const float* partial, int32_t nblk, float inv_denom, float* loss,
                                            gnn_stream_t stream);
 
-extern "C" gnn_status gnn_gat_out_ce_f32(const gnn_graph* g, const gnn_gat_fwd_params* p, const int64_t* y,
-                                         const uint8_t* mask, const float* class_w, float inv_denom, float* dlogits,
-                                         int64_t ld_d, float* colsum, float* loss, void* workspace,
-                                         size_t workspace_bytes, gnn_stream_t stream) {
-  const char* fn = __func__;
+static gnn_status gat_out_ce(const char* fn, const gnn_graph* g, const gnn_gat_fwd_params* p, const gnn_ce_spec* sp,
+                             float* dlogits, int64_t ld_d, float* colsum, float* loss, void* workspace,
+                             size_t workspace_bytes, gnn_stream_t stream) {
   if (!g || !p) return fail(GNN_ERR_INVALID_ARG, fn, "null graph or params");
   if (p->heads != 1 || p->chans < 1 || p->chans > 2 || p->concat || p->act != GNN_ACT_NONE || p->dropout_p != 0.0f ||
       p->edge_w)
@@ -1839,8 +1846,10 @@ extern "C" gnn_status gnn_gat_out_ce_f32(const gnn_graph* g, const gnn_gat_fwd_p
   if (N < 1 || !p->xh || !p->att_src || !p->att_dst || !p->a_src || !p->a_dst || !p->alpha || !p->out || !g->rowptr ||
       (g->num_slots > 0 && !g->col))
     return fail(GNN_ERR_INVALID_ARG, fn, "null operand / N < 1");
-  const bool ce = y != nullptr;
-  if (ce && (!mask || !class_w || !dlogits || ld_d < p->chans)) return fail(GNN_ERR_INVALID_ARG, fn, "CE operands");
+  const bool ce = sp != nullptr && sp->y != nullptr;
+  if (ce && (!sp->mask || !sp->class_w || !dlogits || ld_d < p->chans)) return fail(GNN_ERR_INVALID_ARG, fn, "CE operands");
+  if (ce && sp->focal && !(sp->focal_gamma >= 1.0f))
+    return fail(GNN_ERR_INVALID_ARG, fn, "focal_gamma < 1 (unbounded gradient at p = 1)");
   const int nblk = (int)ceil_div(N, 256);
   if (ce && (!workspace || workspace_bytes < (size_t)nblk * sizeof(float)))
     return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
@@ -1853,10 +1862,27 @@ extern "C" gnn_status gnn_gat_out_ce_f32(const gnn_graph* g, const gnn_gat_fwd_p
     gat_out_narrow_kernel<false><<<(unsigned)nblk, 256, 0, st>>>(a);
     return hip_check(hipGetLastError(), fn);
   }
-  a.ce_y = y; a.ce_mask = mask; a.ce_w = class_w; a.ce_inv = inv_denom; a.ce_dl = dlogits; a.ce_ldd = ld_d;
+  a.ce_y = sp->y; a.ce_mask = sp->mask; a.ce_w = sp->class_w; a.ce_inv = sp->inv_denom; a.ce_dl = dlogits; a.ce_ldd = ld_d;
   a.ce_part = static_cast<float*>(workspace); a.ce_cs = colsum;
-  gat_out_narrow_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  a.ce_rw = sp->row_w; a.ce_focal = sp->focal; a.ce_gamma = sp->focal_gamma;
+  if (sp->row_w || sp->focal) gat_out_narrow_kernel<true, true><<<(unsigned)nblk, 256, 0, st>>>(a);
+  else gat_out_narrow_kernel<true><<<(unsigned)nblk, 256, 0, st>>>(a);
   const gnn_status s = hip_check(hipGetLastError(), fn);
   if (s != GNN_OK || !loss) return s;  // loss NULL: the partials stay in the workspace (ClipAdam / finish)
-  return gnn_masked_ce_finish(static_cast<float*>(workspace), nblk, inv_denom, loss, stream);
+  return gnn_masked_ce_finish(static_cast<float*>(workspace), nblk, sp->inv_denom, loss, stream);
+}
+
+extern "C" gnn_status gnn_gat_out_ce_f32(const gnn_graph* g, const gnn_gat_fwd_params* p, const int64_t* y,
+                                         const uint8_t* mask, const float* class_w, float inv_denom, float* dlogits,
+                                         int64_t ld_d, float* colsum, float* loss, void* workspace,
+                                         size_t workspace_bytes, gnn_stream_t stream) {
+  gnn_ce_spec sp{};
+  sp.y = y; sp.mask = mask; sp.class_w = class_w; sp.inv_denom = inv_denom;
+  return gat_out_ce(__func__, g, p, &sp, dlogits, ld_d, colsum, loss, workspace, workspace_bytes, stream);
+}
+
+extern "C" gnn_status gnn_gat_out_ce_spec_f32(const gnn_graph* g, const gnn_gat_fwd_params* p, const gnn_ce_spec* spec,
+                                              float* dlogits, int64_t ld_d, float* colsum, float* loss,
+                                              void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
+  return gat_out_ce(__func__, g, p, spec, dlogits, ld_d, colsum, loss, workspace, workspace_bytes, stream);
 }

@@ -32,14 +32,17 @@ __device__ __forceinline__ float block_sum(float v, float* sh) {
 // partial[b] = Σ loss over block b's rows.  colsum (optional, ABI 21): colsum[b·C + c] = Σ dx[:, c]
 // over block b's rows (the same fixed-order block sum): the output layer's bias gradient without
 // a pass over dlogits (gnn_colsum_finish_f32 adds the blocks).
-template <int CT>  // CT > 0: compile-time class count (registers); CT == 0: runtime C <= kMaxClasses
+// VAR (gnn_masked_ce_spec_f32): row_w (optional) and focal / gamma of a gnn_ce_spec (masked_ce_row<CM, true>).
+template <int CT, bool VAR = false>  // CT > 0: compile-time class count (registers); CT == 0: runtime C <= kMaxClasses
 __global__ __launch_bounds__(kCeThreads) void masked_ce_kernel(int64_t N, int Crt, const float* __restrict__ x,
                                                                int64_t ldx, const int64_t* __restrict__ y,
                                                                const uint8_t* __restrict__ mask,
                                                                const float* __restrict__ w, float inv_denom,
                                                                float* __restrict__ dx, int64_t ldd,
                                                                float* __restrict__ partial,
-                                                               float* __restrict__ colsum = nullptr) {
+                                                               float* __restrict__ colsum = nullptr,
+                                                               const float* __restrict__ row_w = nullptr,
+                                                               int focal = 0, float gamma = 0.f) {
   constexpr int CM = CT > 0 ? CT : kMaxClasses;
   const int C = CT > 0 ? CT : Crt;
   __shared__ float sh[kCeThreads / 64];
@@ -54,7 +57,11 @@ __global__ __launch_bounds__(kCeThreads) void masked_ce_kernel(int64_t N, int Cr
     float v[CM];
 #pragma unroll
     for (int c = 0; c < CM; ++c) v[c] = c < C ? x[row * ldx + c] : 0.f;
-    l = masked_ce_row<CM>(v, C, t, on, on ? w[t] : 0.f, inv_denom, dx + row * ldd, dv);
+    if constexpr (VAR)
+      l = masked_ce_row<CM, true>(v, C, t, on, on ? w[t] : 0.f, inv_denom, dx + row * ldd, dv,
+                                  row_w ? row_w[row] : 1.0f, focal != 0, gamma);
+    else
+      l = masked_ce_row<CM>(v, C, t, on, on ? w[t] : 0.f, inv_denom, dx + row * ldd, dv);
   }
   const float t = block_sum(l, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
@@ -394,6 +401,46 @@ extern "C" gnn_status gnn_masked_ce_workspace_size(int64_t N, size_t* bytes) {
   return GNN_OK;
 }
 
+// every masked-CE entry point: the plain spec (row_w NULL, focal 0) runs the plain instantiations
+static gnn_status masked_ce_launch(const char* fn, int64_t N, int32_t C, const float* logits, int64_t ldx,
+                                   const gnn_ce_spec& sp, float* dlogits, int64_t ld_d, float* loss, void* workspace,
+                                   size_t workspace_bytes, float* colsum, gnn_stream_t stream) {
+  const int nblk = (int)std::max<int64_t>(1, ceil_div(N, kCeThreads));
+  if (!workspace || workspace_bytes < nblk * sizeof(float)) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  float* partial = static_cast<float*>(workspace);
+  if (N == 0) {
+    if (!loss) return hip_check(hipMemsetAsync(partial, 0, sizeof(float), st), fn);  // one zero partial
+    return hip_check(hipMemsetAsync(loss, 0, sizeof(float), st), fn);
+  }
+  const bool var = sp.row_w || sp.focal;
+  if (var && C == 2)
+    masked_ce_kernel<2, true><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, sp.y, sp.mask, sp.class_w, sp.inv_denom,
+                                                           dlogits, ld_d, partial, colsum, sp.row_w, sp.focal,
+                                                           sp.focal_gamma);
+  else if (var)
+    masked_ce_kernel<0, true><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, sp.y, sp.mask, sp.class_w, sp.inv_denom,
+                                                           dlogits, ld_d, partial, colsum, sp.row_w, sp.focal,
+                                                           sp.focal_gamma);
+  else if (C == 2)
+    masked_ce_kernel<2><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, sp.y, sp.mask, sp.class_w, sp.inv_denom,
+                                                     dlogits, ld_d, partial, colsum);
+  else
+    masked_ce_kernel<0><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, sp.y, sp.mask, sp.class_w, sp.inv_denom,
+                                                     dlogits, ld_d, partial, colsum);
+  GNN_LAUNCH_CHECK();
+  if (!loss) return GNN_OK;  // the partials stay in the workspace (gnn_masked_ce_finish / ClipAdam)
+  sum_partials_kernel<<<1, 256, 0, st>>>(partial, nblk, sp.inv_denom, loss);
+  GNN_LAUNCH_CHECK();
+  return GNN_OK;
+}
+
+static gnn_ce_spec plain_spec(const int64_t* y, const uint8_t* mask, const float* class_w, float inv_denom) {
+  gnn_ce_spec sp{};
+  sp.y = y; sp.mask = mask; sp.class_w = class_w; sp.inv_denom = inv_denom;
+  return sp;
+}
+
 extern "C" gnn_status gnn_masked_ce_f32(int64_t N, int32_t C, const float* logits, int64_t ldx, const int64_t* y,
                                         const uint8_t* mask, const float* class_w, float inv_denom, float* dlogits,
                                         int64_t ld_d, float* loss, void* workspace, size_t workspace_bytes,
@@ -401,25 +448,8 @@ extern "C" gnn_status gnn_masked_ce_f32(int64_t N, int32_t C, const float* logit
   if (N < 0 || C < 1 || C > kMaxClasses || ldx < C || ld_d < C || (N > 0 && (!logits || !y || !mask ||
                                                                                !class_w || !dlogits)))
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad args (1 <= C <= 16)");
-  const int nblk = (int)std::max<int64_t>(1, ceil_div(N, kCeThreads));
-  if (!workspace || workspace_bytes < nblk * sizeof(float)) return fail(GNN_ERR_WORKSPACE, __func__, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = static_cast<float*>(workspace);
-  if (N == 0) {
-    if (!loss) return hip_check(hipMemsetAsync(partial, 0, sizeof(float), st), __func__);  // one zero partial
-    return hip_check(hipMemsetAsync(loss, 0, sizeof(float), st), __func__);
-  }
-  if (C == 2)
-    masked_ce_kernel<2><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, y, mask, class_w, inv_denom, dlogits, ld_d,
-                                                     partial);
-  else
-    masked_ce_kernel<0><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, y, mask, class_w, inv_denom, dlogits, ld_d,
-                                                     partial);
-  GNN_LAUNCH_CHECK();
-  if (!loss) return GNN_OK;  // the partials stay in the workspace (gnn_masked_ce_finish / ClipAdam)
-  sum_partials_kernel<<<1, 256, 0, st>>>(partial, nblk, inv_denom, loss);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  return masked_ce_launch(__func__, N, C, logits, ldx, plain_spec(y, mask, class_w, inv_denom), dlogits, ld_d, loss,
+                          workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" gnn_status gnn_masked_ce_colsum_f32(int64_t N, int32_t C, const float* logits, int64_t ldx,
@@ -430,21 +460,22 @@ extern "C" gnn_status gnn_masked_ce_colsum_f32(int64_t N, int32_t C, const float
   if (N < 1 || C < 1 || C > kMaxClasses || ldx < C || ld_d < C || !logits || !y || !mask || !class_w ||
       !dlogits || !colsum)
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad args (N >= 1, 1 <= C <= 16, colsum)");
-  const int nblk = (int)ceil_div(N, kCeThreads);
-  if (!workspace || workspace_bytes < nblk * sizeof(float)) return fail(GNN_ERR_WORKSPACE, __func__, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  float* partial = static_cast<float*>(workspace);
-  if (C == 2)
-    masked_ce_kernel<2><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, y, mask, class_w, inv_denom, dlogits, ld_d,
-                                                     partial, colsum);
-  else
-    masked_ce_kernel<0><<<nblk, kCeThreads, 0, st>>>(N, C, logits, ldx, y, mask, class_w, inv_denom, dlogits, ld_d,
-                                                     partial, colsum);
-  GNN_LAUNCH_CHECK();
-  if (!loss) return GNN_OK;
-  sum_partials_kernel<<<1, 256, 0, st>>>(partial, nblk, inv_denom, loss);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  return masked_ce_launch(__func__, N, C, logits, ldx, plain_spec(y, mask, class_w, inv_denom), dlogits, ld_d, loss,
+                          workspace, workspace_bytes, colsum, stream);
+}
+
+extern "C" gnn_status gnn_masked_ce_spec_f32(int64_t N, int32_t C, const float* logits, int64_t ldx,
+                                             const gnn_ce_spec* spec, float* dlogits, int64_t ld_d, float* loss,
+                                             void* workspace, size_t workspace_bytes, float* colsum,
+                                             gnn_stream_t stream) {
+  if (!spec) return fail(GNN_ERR_INVALID_ARG, __func__, "null spec");
+  if (spec->focal && !(spec->focal_gamma >= 1.0f))
+    return fail(GNN_ERR_INVALID_ARG, __func__, "focal_gamma < 1 (unbounded gradient at p = 1)");
+  if (N < 0 || (colsum && N < 1) || C < 1 || C > kMaxClasses || ldx < C || ld_d < C ||
+      (N > 0 && (!logits || !spec->y || !spec->mask || !spec->class_w || !dlogits)))
+    return fail(GNN_ERR_INVALID_ARG, __func__, "bad args (1 <= C <= 16; colsum: N >= 1)");
+  return masked_ce_launch(__func__, N, C, logits, ldx, *spec, dlogits, ld_d, loss, workspace, workspace_bytes, colsum,
+                          stream);
 }
 
 extern "C" gnn_status gnn_masked_ce_finish(const float* partial, int32_t nblk, float inv_denom, float* loss,

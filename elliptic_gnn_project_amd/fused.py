@@ -808,10 +808,12 @@ def _deferring() -> bool:
     return _BUMP_DEFER[0] is not None and torch.cuda.is_current_stream_capturing()
 
 
-def defer_loss_sum(device: torch.device, ws: torch.Tensor, nblk: int, inv_denom: float, loss: torch.Tensor) -> bool:
+def defer_loss_sum(device: torch.device, ws: torch.Tensor, nblk: int, inv_denom: float, loss: torch.Tensor,
+                   allow: bool = True) -> bool:
     """Called by the fused CE: True when its loss scalar is left to the step's end (then the CE
-    launched with loss = NULL and ``ws`` holds its partials until then)."""
-    if not _deferring() or not _BUMP_DEFER[0].defer_loss or device in _PENDING_LOSS:
+    launched with loss = NULL and ``ws`` holds its partials until then).  ``allow`` False (a loss
+    the step adds to before the optimizer, e.g. the time-embedding L2 term): declined."""
+    if not allow or not _deferring() or not _BUMP_DEFER[0].defer_loss or device in _PENDING_LOSS:
         return False
     _PENDING_LOSS[device] = (ws, int(nblk), float(inv_denom), loss)
     _BUMP_DEFER[0].held.append(ws)

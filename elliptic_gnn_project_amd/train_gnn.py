@@ -95,6 +95,10 @@ def _norm_train_time(t_vec, t_min, t_max):
     return (t_vec.float() - float(t_min)) / max(float(t_max - t_min), 1.0)
 
 
+# the loss variants (focal, time weighting, embedding L2) in the fused CE kernels; GNNMP_CE_VARIANTS=0: A/B
+_CE_VARIANTS = os.environ.get("GNNMP_CE_VARIANTS", "1") != "0"
+
+
 def _make_loss_fn(cfg: Dict, cw: torch.Tensor, model, t_min: int, t_max: int, world: int = 1):
     """src/train_gnn.py:136-183.  ``world`` > 1 (timestep-partitioned ranks): the embedding L2
     term is added once per rank, so each rank adds 1/world of it (the all-reduced gradient and
@@ -125,38 +129,77 @@ def _make_loss_fn(cfg: Dict, cw: torch.Tensor, model, t_min: int, t_max: int, wo
         # ``denom``: global sample count for timestep-partitioned data parallelism, so the
         # sum over ranks equals the single-device .mean() (src/train_gnn.py:175).
         loss = loss_vec.mean() if denom is None else loss_vec.sum() / float(denom)
+        return embed_term(loss)
+
+    def embed_term(loss):
         if embed_l2 > 0.0 and getattr(model, "time_emb", None) is not None:
             loss = loss + (embed_l2 / world) * model.time_emb.weight.pow(2).mean()
         return loss
 
+    def class_w(device):
+        w = cw_dev.get(device)
+        if w is None:
+            w = cw_dev[device] = cw.to(device)
+        return w
+
+    rw_cache = {}
+
+    def row_weights(t_all):
+        """The time weights of ALL nodes — loss_fn's own expressions, so each row's weight is the
+        bits the reference computes for it — built once per (timestep tensor, its version)."""
+        key = (t_all.data_ptr(), t_all._version, t_all.numel(), scheme, t_min, t_max)
+        hit = rw_cache.get(t_all.device)
+        if hit is not None and hit[0] == key and hit[1] is t_all:
+            return hit[2]
+        wt = _norm_train_time(t_all, t_min, t_max)
+        if scheme == "sqrt":
+            wt = torch.sqrt(torch.clamp(wt, min=0.0))
+        wt = torch.clamp(wt, min=1e-3).contiguous()
+        rw_cache[t_all.device] = (key, t_all, wt)
+        return wt
+
+    def variant(t_idx_all):
+        """masked_cross_entropy's variant arguments of this configuration."""
+        has_l2 = embed_l2 > 0.0 and getattr(model, "time_emb", None) is not None
+        return dict(row_w=row_weights(t_idx_all) if (scheme != "none" and t_idx_all is not None) else None,
+                    focal_gamma=gamma if focal else None, defer=not has_l2)
+
     def full(logits, y_all, mask, denom=None, t_idx_all=None):
-        """The same loss from the full logits and the row mask: on the GPU in the default
-        configuration one fused kernel (train_ops.masked_cross_entropy); else loss_fn on the rows."""
-        if loss_fn.plain and logits.is_cuda and logits.dtype == torch.float32:
+        """The same loss from the full logits and the row mask: on the GPU one fused kernel
+        (train_ops.masked_cross_entropy) for every fusable configuration — the default, focal with
+        gamma >= 1, either time weighting (``t_idx_all``: every node's timestep) and the embedding
+        L2, whose term is added here as loss_fn adds it; else loss_fn on the rows."""
+        if loss_fn.fusable and logits.is_cuda and logits.dtype == torch.float32:
             from .train_ops import masked_cross_entropy
-            w = cw_dev.get(logits.device)
-            if w is None:
-                w = cw_dev[logits.device] = cw.to(logits.device)
-            return masked_cross_entropy(logits, y_all, mask, w, denom=denom)
+            if loss_fn.plain:
+                return masked_cross_entropy(logits, y_all, mask, class_w(logits.device), denom=denom)
+            return embed_term(masked_cross_entropy(logits, y_all, mask, class_w(logits.device), denom=denom,
+                                                   **variant(t_idx_all)))
         idx = mask.nonzero().squeeze(1)
         t_sel = t_idx_all.index_select(0, idx) if t_idx_all is not None else None
         return loss_fn(logits.index_select(0, idx), y_all.index_select(0, idx), t_sel, denom=denom)
 
-    def target(y_all, mask, denom):
-        """Context for the training forward whose loss is ``full(logits, y_all, mask, denom)``:
-        the forward may compute that masked CE itself (train_ops.fused_ce_target — the fused SAGE
-        output layer does, in its aggregation's launch); a no-op for the other loss variants."""
-        if not (loss_fn.plain and y_all.is_cuda and denom is not None):
+    def target(y_all, mask, denom, t_idx_all=None):
+        """Context for the training forward whose loss is ``full(logits, y_all, mask, denom,
+        t_idx_all)``: the forward may compute that masked CE itself (train_ops.fused_ce_target —
+        the fused SAGE output layer does, in its aggregation's launch); a no-op for a loss that is
+        not fusable."""
+        if not (loss_fn.fusable and y_all.is_cuda and denom is not None):
             return contextlib.nullcontext()
         from .train_ops import fused_ce_target
 
-        w = cw_dev.get(y_all.device)
-        if w is None:
-            w = cw_dev[y_all.device] = cw.to(y_all.device)
-        return fused_ce_target(y_all, mask, w, denom)
+        if loss_fn.plain:
+            return fused_ce_target(y_all, mask, class_w(y_all.device), denom)
+        return fused_ce_target(y_all, mask, class_w(y_all.device), denom, **variant(t_idx_all))
 
     loss_fn.plain = not focal and scheme == "none" and embed_l2 == 0.0
+    # fusable: the loss runs in the fused CE kernels (plain, or a variant gnn_ce_spec describes);
+    # focal with gamma < 1 (unbounded gradient at p = 1) and GNNMP_CE_VARIANTS=0 (A/B: the routing
+    # before the variants were fused) keep the torch loss
+    loss_fn.fusable = loss_fn.plain or (_CE_VARIANTS and scheme in ("none", "linear", "sqrt")
+                                        and (not focal or gamma >= 1.0))
     loss_fn.full = full
+    loss_fn.row_weights = row_weights
     loss_fn.target = target
     return loss_fn
 
@@ -223,15 +266,18 @@ def train_epoch(model, data, edge_index, optimizer, loss_fn, scaler, use_amp, cf
     # AMP on an fp32 libgnnmp model (amp_is_exact): the fused step, GradScaler's scale / unscale
     # left out (exact on fp32 gradients) and its skip of a non-finite update done by ClipAdam
     amp_fused = use_amp and getattr(optimizer, "skip_nonfinite", False)
-    fused_ce = getattr(loss_fn, "plain", False) and (not use_amp or amp_fused) and denom is not None
+    fusable = getattr(loss_fn, "fusable", getattr(loss_fn, "plain", False))
+    fused_ce = fusable and (not use_amp or amp_fused) and denom is not None
+    weighted = cfg.get("time_loss_weighting", "none") != "none"
     with _autocast(device, use_amp):
-        with (loss_fn.target(data.y, data.train_mask, denom) if fused_ce else contextlib.nullcontext()):
+        with (loss_fn.target(data.y, data.train_mask, denom, data.timestep if weighted else None) if fused_ce
+              else contextlib.nullcontext()):
             logits = model(data.x, edge_index, data.timestep if _model_uses_time_embed(model) else None)
-        t_idx = _rows(data.timestep, data, "train") if cfg.get("time_loss_weighting", "none") != "none" else None
-        if (getattr(loss_fn, "plain", False) and logits.is_cuda and logits.dtype == torch.float32
-                and (not use_amp or amp_fused)):
-            loss = loss_fn.full(logits, data.y, data.train_mask, denom=denom)
+        if fusable and logits.is_cuda and logits.dtype == torch.float32 and (not use_amp or amp_fused):
+            loss = loss_fn.full(logits, data.y, data.train_mask, denom=denom,
+                                t_idx_all=data.timestep if weighted else None)
         else:
+            t_idx = _rows(data.timestep, data, "train") if weighted else None
             loss = loss_fn(_rows(logits, data, "train"), _rows(data.y, data, "train"), t_idx,
                            denom=denom if bucket is not None else None)
     if (scaler.is_enabled() and not amp_fused) or not loss.is_cuda:

@@ -49,12 +49,28 @@ def unit_gradient(device) -> torch.Tensor:
 _CE_COLSUM = os.environ.get("GNNMP_CE_COLSUM", "1") != "0"
 
 
+def _ce_variant(var):
+    """(row_w, focal_gamma, defer) of a CE target's optional sixth field (None: the plain loss)."""
+    return (None, None, True) if var is None else var
+
+
+def _ce_spec(y, m8, w, inv, row_w, gamma):
+    """The gnn_ce_spec of a variant loss (row weights and / or focal; include/gnnmp.h).  Neither
+    (a loss that only must not be deferred): the library runs the plain kernels on it."""
+    sp = _lib.GnnCeSpec()
+    sp.y, sp.mask, sp.class_w, sp.row_w = y.data_ptr(), m8.data_ptr(), w.data_ptr(), _lib.ptr(row_w)
+    sp.inv_denom = float(inv)
+    sp.focal, sp.focal_gamma = (0, 0.0) if gamma is None else (1, float(gamma))
+    return sp
+
+
 class _MaskedCE(torch.autograd.Function):
     """dlogits is written into the right half of an [N, 2C] buffer (``dl._gnnmp_dz``): the fused
     SAGE backward needs dz = [meanᵀ(dlogits) | dlogits] and fills only the left half (no copy)."""
 
     @staticmethod
-    def forward(ctx, logits, y, mask_u8, class_w, inv_denom: float):
+    def forward(ctx, logits, y, mask_u8, class_w, inv_denom: float, var=None):
+        row_w, gamma, defer = _ce_variant(var)
         logits = logits.contiguous()
         N, C = logits.shape
         buf = torch.empty((N, 2 * C), dtype=logits.dtype, device=logits.device)
@@ -64,12 +80,18 @@ class _MaskedCE(torch.autograd.Function):
         from .fused import defer_loss_sum
 
         nblk = max(1, -(-N // 256))  # gnn_masked_ce_f32's partials (256-row blocks)
-        deferred = defer_loss_sum(logits.device, ws, nblk, float(inv_denom), loss)  # captured step: at its end
+        deferred = defer_loss_sum(logits.device, ws, nblk, float(inv_denom), loss, allow=defer)  # captured step: at its end
         args = (N, C, logits.data_ptr(), C, y.data_ptr(), mask_u8.data_ptr(), class_w.data_ptr(), float(inv_denom),
                 dl.data_ptr(), 2 * C, None if deferred else loss.data_ptr(), ws.data_ptr(), ws.numel() * 4)
         ctx.colsum = None
         if N > 0 and _CE_COLSUM:  # the blocks' column sums of dlogits too: the output layer's bias gradient (colsum_of)
             ctx.colsum = torch.empty(nblk * C, dtype=torch.float32, device=logits.device)
+        if var is not None:  # a loss variant: the spec entry (row weights, focal)
+            _lib.call("gnn_masked_ce_spec_f32", N, C, logits.data_ptr(), C,
+                      _ce_spec(y, mask_u8, class_w, inv_denom, row_w, gamma), dl.data_ptr(), 2 * C,
+                      None if deferred else loss.data_ptr(), ws.data_ptr(), ws.numel() * 4, _lib.ptr(ctx.colsum),
+                      _lib.stream_handle(logits.device))
+        elif ctx.colsum is not None:
             _lib.call("gnn_masked_ce_colsum_f32", *args, ctx.colsum.data_ptr(), _lib.stream_handle(logits.device))
         else:
             _lib.call("gnn_masked_ce_f32", *args, _lib.stream_handle(logits.device))
@@ -86,8 +108,8 @@ class _MaskedCE(torch.autograd.Function):
             dl._gnnmp_dz = buf
             if ctx.colsum is not None:
                 dl._gnnmp_colsum = ctx.colsum
-            return dl, None, None, None, None
-        return dl * g, None, None, None, None
+            return dl, None, None, None, None, None
+        return dl * g, None, None, None, None, None
 
 
 class _PrecomputedCE(torch.autograd.Function):
@@ -119,16 +141,30 @@ class _PrecomputedCE(torch.autograd.Function):
         return dl * g, None
 
 
-_CE_TARGET = [None]  # (key, y, mask_u8, class_w, inv_denom) of the active fused_ce_target
+_CE_TARGET = [None]  # (key, y, mask_u8, class_w, inv_denom[, variant]) of the active fused_ce_target
 
 
-def _ce_operands(y, mask, class_w, denom, device):
+def _ce_operands(y, mask, class_w, denom, device, row_w=None, focal_gamma=None, defer=True):
+    """The CE's operands as the kernels take them, with the key that tells two losses apart.  A
+    loss variant (``row_w`` [N] per-row weights, ``focal_gamma``) or a loss that must not be
+    deferred (``defer`` False: something is added to it before the optimizer) appends a sixth
+    field (row_w, focal_gamma, defer) and extends the key by it; the plain loss stays five fields."""
     m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
     w = class_w.to(device=device, dtype=torch.float32).contiguous()
     y = y.contiguous()
     m8 = m8.contiguous()
     inv = 1.0 / float(denom)
-    return (y.data_ptr(), m8.data_ptr(), w.data_ptr(), inv), y, m8, w, inv
+    key = (y.data_ptr(), m8.data_ptr(), w.data_ptr(), inv)
+    if row_w is None and focal_gamma is None and defer:
+        return key, y, m8, w, inv
+    if focal_gamma is not None and not float(focal_gamma) >= 1.0:
+        raise ValueError("the fused focal loss needs focal_gamma >= 1 (its gradient is unbounded at p = 1 below that)")
+    if row_w is not None:
+        row_w = row_w.to(device=device, dtype=torch.float32).contiguous()
+        if row_w.numel() != y.numel():
+            raise ValueError("row_w has one weight per row of the logits")
+    gamma = None if focal_gamma is None else float(focal_gamma)
+    return key + (_lib.ptr(row_w), gamma, bool(defer)), y, m8, w, inv, (row_w, gamma, bool(defer))
 
 
 class fused_ce_target:
@@ -138,15 +174,18 @@ class fused_ce_target:
     the CE in one launch, bit for bit the two launches' results) and masked_cross_entropy then
     returns that result instead of launching the CE.  Every other consumer of the logits sees the
     same logits; a loss with other operands falls back to its own launch.  ``denom`` must be given
-    (no host sync)."""
+    (no host sync).  ``row_w`` / ``focal_gamma`` / ``defer``: the loss variant, as
+    masked_cross_entropy takes it."""
 
-    def __init__(self, y: torch.Tensor, mask: torch.Tensor, class_w: torch.Tensor, denom: float):
+    def __init__(self, y: torch.Tensor, mask: torch.Tensor, class_w: torch.Tensor, denom: float, row_w=None,
+                 focal_gamma=None, defer: bool = True):
         self.args = (y, mask, class_w, denom)
+        self.variant = (row_w, focal_gamma, defer)
 
     def __enter__(self):
         y, mask, class_w, denom = self.args
         if y.is_cuda and float(denom) != 0.0:
-            _CE_TARGET[0] = _ce_operands(y, mask, class_w, denom, y.device)
+            _CE_TARGET[0] = _ce_operands(y, mask, class_w, denom, y.device, *self.variant)
         return self
 
     def __exit__(self, *exc):
@@ -155,7 +194,8 @@ class fused_ce_target:
 
 
 def ce_target():
-    """The active fused_ce_target's (key, y, mask_u8, class_w, inv_denom), or None."""
+    """The active fused_ce_target's (key, y, mask_u8, class_w, inv_denom[, variant]), or None:
+    opaque to the layers, which hand it to sage_out_mean_ce / gcn_out_ce / gat_out."""
     return _CE_TARGET[0]
 
 
@@ -165,7 +205,8 @@ def sage_out_mean_ce(plan, z: torch.Tensor, C: int, bias, target, colsum: bool =
     ``colsum``: also dlogits' block column sums (the output bias gradient, aggregation.colsum_of)."""
     from .fused import defer_loss_sum
 
-    key, y, m8, w, inv = target
+    key, y, m8, w, inv, *var = target
+    row_w, gamma, defer = _ce_variant(var[0] if var else None)
     N, dev = z.size(0), z.device
     logits = torch.empty((N, C), dtype=torch.float32, device=dev)
     buf = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)
@@ -173,12 +214,18 @@ def sage_out_mean_ce(plan, z: torch.Tensor, C: int, bias, target, colsum: bool =
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ws = _ws(_ce_ws_bytes(N), dev)
     nblk = max(1, -(-N // 256))
-    deferred = defer_loss_sum(dev, ws, nblk, inv, loss)  # captured step with defer_loss: at its end
+    deferred = defer_loss_sum(dev, ws, nblk, inv, loss, allow=defer)  # captured step with defer_loss: at its end
     cs = torch.empty(nblk * C, dtype=torch.float32, device=dev) if (colsum and _CE_COLSUM) else None
-    _lib.call("gnn_sage_out_mean_ce_f32", plan.c_graph, plan.deg.data_ptr(), z.data_ptr(), int(z.stride(0)), int(C),
-              _lib.ptr(bias), logits.data_ptr(), C, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
-              buf.data_ptr() + C * 4, 2 * C, u.data_ptr(), C, _lib.ptr(cs), None if deferred else loss.data_ptr(),
-              ws.data_ptr(), ws.numel() * 4, _lib.stream_handle(dev))
+    if var:  # a loss variant: the spec entry
+        _lib.call("gnn_sage_out_mean_ce_spec_f32", plan.c_graph, plan.deg.data_ptr(), z.data_ptr(), int(z.stride(0)),
+                  int(C), _lib.ptr(bias), logits.data_ptr(), C, _ce_spec(y, m8, w, inv, row_w, gamma),
+                  buf.data_ptr() + C * 4, 2 * C, u.data_ptr(), C, _lib.ptr(cs), None if deferred else loss.data_ptr(),
+                  ws.data_ptr(), ws.numel() * 4, _lib.stream_handle(dev))
+    else:
+        _lib.call("gnn_sage_out_mean_ce_f32", plan.c_graph, plan.deg.data_ptr(), z.data_ptr(), int(z.stride(0)), int(C),
+                  _lib.ptr(bias), logits.data_ptr(), C, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
+                  buf.data_ptr() + C * 4, 2 * C, u.data_ptr(), C, _lib.ptr(cs), None if deferred else loss.data_ptr(),
+                  ws.data_ptr(), ws.numel() * 4, _lib.stream_handle(dev))
     buf._gnnmp_u = u
     if cs is not None:
         buf._gnnmp_colsum = cs
@@ -192,7 +239,8 @@ def gcn_out_ce(plan, t: torch.Tensor, bias, target):
     for _PrecomputedCE."""
     from .fused import defer_loss_sum
 
-    key, y, m8, w, inv = target
+    key, y, m8, w, inv, *var = target
+    row_w, gamma, defer = _ce_variant(var[0] if var else None)
     N, C, dev = t.size(0), t.size(1), t.device
     logits = torch.empty((N, C), dtype=torch.float32, device=dev)
     buf = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)
@@ -200,11 +248,17 @@ def gcn_out_ce(plan, t: torch.Tensor, bias, target):
     ws = _ws(_ce_ws_bytes(N), dev)
     nblk = max(1, -(-N // 256))
     cs = torch.empty(nblk * C, dtype=torch.float32, device=dev) if _CE_COLSUM else None
-    deferred = defer_loss_sum(dev, ws, nblk, inv, loss)
-    _lib.call("gnn_gcn_out_ce_f32", plan.c_graph, plan.dinv.data_ptr(), t.data_ptr(), int(t.stride(0)), int(C),
-              _lib.ptr(bias), logits.data_ptr(), C, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
-              buf.data_ptr() + C * 4, 2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(),
-              ws.numel() * 4, _lib.stream_handle(dev))
+    deferred = defer_loss_sum(dev, ws, nblk, inv, loss, allow=defer)
+    if var:  # a loss variant: the spec entry
+        _lib.call("gnn_gcn_out_ce_spec_f32", plan.c_graph, plan.dinv.data_ptr(), t.data_ptr(), int(t.stride(0)), int(C),
+                  _lib.ptr(bias), logits.data_ptr(), C, _ce_spec(y, m8, w, inv, row_w, gamma), buf.data_ptr() + C * 4,
+                  2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                  _lib.stream_handle(dev))
+    else:
+        _lib.call("gnn_gcn_out_ce_f32", plan.c_graph, plan.dinv.data_ptr(), t.data_ptr(), int(t.stride(0)), int(C),
+                  _lib.ptr(bias), logits.data_ptr(), C, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
+                  buf.data_ptr() + C * 4, 2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(),
+                  ws.numel() * 4, _lib.stream_handle(dev))
     if cs is not None:
         buf._gnnmp_colsum = cs
     return logits, (key, loss, buf, ws)
@@ -223,26 +277,38 @@ def gat_out(plan, p, target=None):
         _lib.call("gnn_gat_out_ce_f32", plan.c_graph, p, None, None, None, 0.0, None, 0, None, None, None, 0,
                   _lib.stream_handle(dev))
         return None
-    key, y, m8, w, inv = target
+    key, y, m8, w, inv, *var = target
+    row_w, gamma, defer = _ce_variant(var[0] if var else None)
     buf = torch.empty((N, 2 * C), dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     ws = _ws(_ce_ws_bytes(N), dev)
     nblk = max(1, -(-N // 256))
     cs = torch.empty(nblk * C, dtype=torch.float32, device=dev) if _CE_COLSUM else None
-    deferred = defer_loss_sum(dev, ws, nblk, inv, loss)
-    _lib.call("gnn_gat_out_ce_f32", plan.c_graph, p, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
-              buf.data_ptr() + C * 4, 2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(),
-              ws.numel() * 4, _lib.stream_handle(dev))
+    deferred = defer_loss_sum(dev, ws, nblk, inv, loss, allow=defer)
+    if var:  # a loss variant: the spec entry
+        _lib.call("gnn_gat_out_ce_spec_f32", plan.c_graph, p, _ce_spec(y, m8, w, inv, row_w, gamma),
+                  buf.data_ptr() + C * 4, 2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(),
+                  ws.numel() * 4, _lib.stream_handle(dev))
+    else:
+        _lib.call("gnn_gat_out_ce_f32", plan.c_graph, p, y.data_ptr(), m8.data_ptr(), w.data_ptr(), float(inv),
+                  buf.data_ptr() + C * 4, 2 * C, _lib.ptr(cs), None if deferred else loss.data_ptr(), ws.data_ptr(),
+                  ws.numel() * 4, _lib.stream_handle(dev))
     if cs is not None:
         buf._gnnmp_colsum = cs
     return (key, loss, buf, ws)
 
 
 def masked_cross_entropy(logits: torch.Tensor, y: torch.Tensor, mask: torch.Tensor, class_w: torch.Tensor,
-                         denom: float | None = None) -> torch.Tensor:
+                         denom: float | None = None, row_w: torch.Tensor | None = None,
+                         focal_gamma: float | None = None, defer: bool = True) -> torch.Tensor:
     """Σ_{i: mask_i} CE_w(logits_i, y_i) / denom (denom defaults to mask.sum(): the reference's .mean()).
 
     ``mask`` is a bool/uint8 [N] tensor, ``y`` int64 [N] (labels of unmasked rows are ignored).
+    The loss variants of ``_make_loss_fn`` run in the same kernel (gnn_masked_ce_spec_f32):
+    ``row_w`` [N] multiplies each row's loss (the time weighting) and
+    ``focal_gamma`` >= 1 makes the row's loss the focal (1 - p)^γ · CE, without the class weight as
+    in the reference.  ``defer`` False: a captured step does not leave this loss's sum to its end
+    (the caller adds to the loss before the optimizer).
     """
     if not logits.is_cuda:
         raise RuntimeError("masked_cross_entropy runs on the GPU (libgnnmp); use the ATen loss on CPU")
@@ -253,11 +319,12 @@ def masked_cross_entropy(logits: torch.Tensor, y: torch.Tensor, mask: torch.Tens
     if float(denom) == 0.0:
         # empty selection: the reference's loss_vec.mean() is NaN and its gradient is zero
         return logits.sum() * 0.0 + float("nan")
-    key, y, m8, w, inv = _ce_operands(y, mask, class_w, denom, logits.device)  # bool mask: no copy
+    key, y, m8, w, inv, *var = _ce_operands(y, mask, class_w, denom, logits.device, row_w, focal_gamma,
+                                            defer)  # bool mask: no copy
     ce = getattr(logits, "_gnnmp_ce", None)
     if ce is not None and ce[0] == key:  # the forward already computed it (fused_ce_target)
         return _PrecomputedCE.apply(logits, ce)
-    return _MaskedCE.apply(logits, y, m8, w, inv)
+    return _MaskedCE.apply(logits, y, m8, w, inv, var[0] if var else None)
 
 
 # Σg² folded into the gradients' producer (ABI 20).  A ClipAdam registers (partials buffer, step

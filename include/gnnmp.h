@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 26
+#define GNNMP_ABI_VERSION 27
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -670,6 +670,49 @@ gnn_status gnn_masked_ce_f32(int64_t N, int32_t C, const float* logits, int64_t 
                              const uint8_t* mask, const float* class_w, float inv_denom, float* dlogits,
                              int64_t ld_d, float* loss, void* workspace, size_t workspace_bytes,
                              gnn_stream_t stream);
+
+/* The masked CE's loss variants (ABI 27; src/train_gnn.py:136-183): one description of the loss for
+ * every CE entry point, so a new variant is a field here and not an argument of each of them.
+ *   base_i = focal ? -(1 - p)^gamma · log p          (no class weight: the reference's focal drops it)
+ *                  : -class_w[y_i] · log p           (p = softmax(x_i)[y_i])
+ *   loss_i = row_w[i] · base_i                       (row_w NULL: 1; the time weighting, built by the host)
+ *   *loss  = Σ loss_i · inv_denom,  dlogits = d(*loss)/dx
+ * on rows with mask[i] != 0 and 0 <= y[i] < C, zero elsewhere.  1 - p is formed from the other
+ * classes' exponentials, so it keeps its relative accuracy as p -> 1; gamma 1 and 2 are plain
+ * products ((1 - p)^0 = 1 also at p = 1).  focal with gamma < 1 is GNN_ERR_INVALID_ARG: its
+ * gradient is unbounded at p = 1.  row_w = NULL, focal = 0 is exactly the entry point without
+ * _spec (the same kernel, bit for bit).  reserved: zero. */
+typedef struct {
+  const int64_t* y;       /* [N] labels */
+  const uint8_t* mask;    /* [N] row mask */
+  const float* class_w;   /* [C] class weights (never NULL; the focal loss does not apply them) */
+  const float* row_w;     /* [N] per-row weights, or NULL */
+  float inv_denom;
+  int32_t focal;          /* 0 / 1 */
+  float focal_gamma;      /* >= 1 when focal */
+  int32_t reserved[5];
+} gnn_ce_spec;
+
+/* gnn_masked_ce_f32 / gnn_masked_ce_colsum_f32 (colsum optional here; with it N >= 1) of a spec. */
+gnn_status gnn_masked_ce_spec_f32(int64_t N, int32_t C, const float* logits, int64_t ldx, const gnn_ce_spec* spec,
+                                  float* dlogits, int64_t ld_d, float* loss, void* workspace,
+                                  size_t workspace_bytes, float* colsum, gnn_stream_t stream);
+/* gnn_sage_out_mean_ce_f32, gnn_gcn_out_ce_f32 and gnn_gat_out_ce_f32 of a spec (spec NULL in the
+ * GAT form: no CE), each with the C limits and the u / colsum / loss / workspace contract of the
+ * entry point it stands beside; the results equal that layer's own launch followed by
+ * gnn_masked_ce_spec_f32 bit for bit. */
+gnn_status gnn_sage_out_mean_ce_spec_f32(const gnn_graph* g, const float* deg, const float* z, int64_t ldz,
+                                         int32_t C, const float* bias, float* logits, int64_t ldo,
+                                         const gnn_ce_spec* spec, float* dlogits, int64_t ld_d, float* u,
+                                         int64_t ldu, float* colsum, float* loss, void* workspace,
+                                         size_t workspace_bytes, gnn_stream_t stream);
+gnn_status gnn_gcn_out_ce_spec_f32(const gnn_graph* g, const float* dinv, const float* t, int64_t ldt, int32_t C,
+                                   const float* bias, float* logits, int64_t ldo, const gnn_ce_spec* spec,
+                                   float* dlogits, int64_t ld_d, float* colsum, float* loss, void* workspace,
+                                   size_t workspace_bytes, gnn_stream_t stream);
+gnn_status gnn_gat_out_ce_spec_f32(const gnn_graph* g, const gnn_gat_fwd_params* p, const gnn_ce_spec* spec,
+                                   float* dlogits, int64_t ld_d, float* colsum, float* loss, void* workspace,
+                                   size_t workspace_bytes, gnn_stream_t stream);
 
 /* clip_grad_norm_(max_norm) + torch.optim.Adam.step() (weight_decay as L2 on the gradient) over
  * up to GNN_ADAM_MAX_TENSORS parameters (src/train_gnn.py:203-206).  `step` is a device float
