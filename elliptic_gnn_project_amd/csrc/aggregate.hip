@@ -1241,38 +1241,6 @@ __global__ __launch_bounds__(256) void agg_flat_pieces_kernel(AggArgs a, int32_t
   else agg_flat_body<MODE, VEC, LPS, NCHMAX>(a, rpg, blockIdx.x - pblocks);
 }
 
-// Narrow rows (F <= 8): one wave per piece, lanes over its <= 64 slots, fixed xor tree.
-template <int MODE>
-__global__ __launch_bounds__(256) void agg_piece_narrow_kernel(AggArgs a, int64_t npieces, const int32_t* piece_seg) {
-  const int lane = threadIdx.x & 63;
-  const int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  if (p >= npieces) return;
-  const int32_t r = piece_seg[p];
-  const int32_t k = (int32_t)p - a.piece0[r];
-  if (k == 0) return;
-  const int32_t beg = a.fptr[r] + k * a.seg_len;
-  const int32_t end = min(beg + a.seg_len, a.fptr[r + 1]);
-  const int32_t slot = beg + lane;
-  const bool ok = slot < end;
-  const int32_t n = a.fnbr[ok ? slot : beg];
-  float acc[8];
-#pragma unroll
-  for (int f = 0; f < 8; ++f) {
-    float v[1] = {(ok && f < a.F) ? a.x[(int64_t)n * a.ldx + f] : 0.0f};
-    if (ok && f < a.F) contrib<MODE, 1>(a, n, r, slot, f, v);
-    acc[f] = v[0];
-  }
-#pragma unroll
-  for (int f = 0; f < 8; ++f)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) acc[f] += __shfl_xor(acc[f], off);
-  if (lane == 0) {
-#pragma unroll
-    for (int f = 0; f < 8; ++f)
-      if (f < a.F) a.part[p * a.F + f] = acc[f];
-  }
-}
-
 // Combine: one wave per long segment, its pieces' partials added in piece order, then the
 // mode's finish (mean divide, root addend, bias, ReLU) and the store.
 template <int MODE, int VEC, int NCH>
@@ -1307,159 +1275,155 @@ bool aligned(const void* p, int bytes) { return p == nullptr || (reinterpret_cas
 // Kernel-lab knob: the constant 0 in libgnnmp.so (no global mutable state, no lab kernels
 // instantiated).  `make lab` compiles this file again with -DGNNMP_AGG_LAB into
 // _lab/libgnnmp_agglab.so, whose gnnx_set_agg_variant selects the lab launch shapes
-// (profiles/lab_agg.py, lab_order.py, tests/test_gpu_order.py).
+// (profiles/lab_agg.py, lab_order.py, tests/test_gpu_order.py).  AggLab is what the knob
+// overrides; libgnnmp.so sees the defaults as constants.
+struct AggLab {
+  int rpg = 0;  // rows per lane group: 0 the product's choice, -1 lps - 1 (lab 5 / 6 / 8 / 9: 4 / 8 / lps - 1 / 1)
+  // 16 rows per wave.  r08 lab (profiles/lab_agg.py, SAGE preset F = 166 CSR, 89.4 us = 63 %
+  // of HBM): 8 rows 89.2, 4 rows 95.7, 32 rows 99.1; U = 4 rows in flight 91.9; a 168-float
+  // padded pitch (dwordx4, one load per row) 89.0 — the gather is not instruction-bound.
+  // XCD-grouped block order (each XCD sweeping one contiguous eighth of the rows) measured
+  // slower with cold caches (r10: 130.4 -> 138.5 us).  Lab 1 / 2 / 3: 8 / 4 / 32 rows.
+  int rpw = 16;
+  bool prefetch = false;    // lab 10, 11 (= 9 + 10): neighbour-id prefetch (r14: 5-10 us slower)
+  bool no_fold = false;     // lab 16: split pieces never in the main pass's launch
+  bool no_split = false;    // lab 7
+  bool wave_split = false;  // lab 12 / 13 / 14: the split, degree-ordered, for the wave-wide gather
+                            // (33 <= F / vec <= 128) too, 16 / 4 / 8 rows per wave
+  bool lane_walk = false;   // lab 15: narrow LDS form, each lane walks its whole row (COOP = false)
+};
 #ifdef GNNMP_AGG_LAB
 int g_agg_lab_variant = 0;
+AggLab agg_lab() {
+  const int v = g_agg_lab_variant;
+  AggLab l;
+  l.rpg = v == 5 ? 4 : v == 6 ? 8 : v == 8 ? -1 : (v == 9 || v == 11) ? 1 : 0;
+  l.rpw = (v == 1 || v == 14) ? 8 : (v == 2 || v == 13) ? 4 : v == 3 ? 32 : 16;
+  l.prefetch = v == 10 || v == 11; l.no_fold = v == 16; l.no_split = v == 7;
+  l.wave_split = v >= 12 && v <= 14; l.lane_walk = v == 15;
+  return l;
+}
 #else
-constexpr int g_agg_lab_variant = 0;
+constexpr AggLab agg_lab() { return {}; }
 #endif
 
-template <int MODE, int VEC, int NCH>
-void launch_split_passes(const AggArgs& a, const gnn_split* sp, hipStream_t st) {
-  if (sp->num_pieces > sp->num_long)
-    agg_piece_wide_kernel<MODE, VEC, NCH><<<(unsigned)ceil_div(sp->num_pieces * 64, 256), 256, 0, st>>>(
-        a, sp->num_pieces, sp->piece_seg);
-  agg_combine_kernel<MODE, VEC, NCH><<<(unsigned)ceil_div(sp->num_long * 64, 256), 256, 0, st>>>(
-      a, sp->num_long, sp->long_seg);
+// The run-time vector width as a compile-time constant: f(std::integral_constant<int, vec>).
+template <class Fn>
+void with_vec(int vec, Fn&& f) {
+  if (vec == 4) f(std::integral_constant<int, 4>{});
+  else if (vec == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
 }
 
-template <int MODE, int VEC>
-void launch_split_v(const AggArgs& a, const gnn_split* sp, hipStream_t st) {
-  const int nch = (int)ceil_div(a.F / VEC, 64);
-  // (r12: 16- / 32-lane groups per piece and per combined row, 4 / 2 per wave, measured 6 us slower
-  // per F = 64 pass than one wave each — per-lane id loads and divergent piece lengths)
-  if (nch <= 1) launch_split_passes<MODE, VEC, 1>(a, sp, st);
-  else if (nch <= 2) launch_split_passes<MODE, VEC, 2>(a, sp, st);
-  else launch_split_passes<MODE, VEC, 4>(a, sp, st);
-}
+// lanes per row of the lane-group gather
+int flat_lps(int nchunk) { return nchunk <= 8 ? 8 : nchunk <= 16 ? 16 : nchunk <= 32 ? 32 : 64; }
 
-
-template <int MODE>
-gnn_status launch_mode(const AggArgs& a, int vec, hipStream_t st, const gnn_split* sp,
-                       const gnn_split* pieces = nullptr, bool* pieces_done = nullptr);
-
-template <int MODE>
-gnn_status launch_mode_split(const AggArgs& a, int vec, hipStream_t st, const gnn_split* sp) {
-  bool pieces_done = false;  // the lane-group main pass takes the pieces into its own launch
-  gnn_status s = launch_mode<MODE>(a, vec, st, nullptr, sp, &pieces_done);  // main pass over the truncated segments
-  if (s != GNN_OK || sp->num_long == 0) return s;
-  if (pieces_done) {
-    const int nch = (int)ceil_div(a.F / vec, 64);
-    if (vec == 4 && nch <= 1) agg_combine_kernel<MODE, 4, 1><<<(unsigned)ceil_div(sp->num_long * 64, 256), 256, 0, st>>>(a, sp->num_long, sp->long_seg);
-    else if (vec == 2 && nch <= 1) agg_combine_kernel<MODE, 2, 1><<<(unsigned)ceil_div(sp->num_long * 64, 256), 256, 0, st>>>(a, sp->num_long, sp->long_seg);
-    else agg_combine_kernel<MODE, 1, 1><<<(unsigned)ceil_div(sp->num_long * 64, 256), 256, 0, st>>>(a, sp->num_long, sp->long_seg);
-    return hip_check(hipGetLastError(), "gnn_aggregate_f32 (split combine)");
-  }
-  if (a.F <= 8) {
-    if (sp->num_pieces > sp->num_long)
-      agg_piece_narrow_kernel<MODE><<<(unsigned)ceil_div(sp->num_pieces * 64, 256), 256, 0, st>>>(
-          a, sp->num_pieces, sp->piece_seg);
-    agg_combine_kernel<MODE, 1, 1><<<(unsigned)ceil_div(sp->num_long * 64, 256), 256, 0, st>>>(
-        a, sp->num_long, sp->long_seg);
-  } else if (vec == 4) {
-    launch_split_v<MODE, 4>(a, sp, st);
-  } else if (vec == 2) {
-    launch_split_v<MODE, 2>(a, sp, st);
-  } else {
-    launch_split_v<MODE, 1>(a, sp, st);
-  }
-  return hip_check(hipGetLastError(), "gnn_aggregate_f32 (split passes)");
-}
-
-template <int MODE>
-gnn_status launch_mode(const AggArgs& a, int vec, hipStream_t st, const gnn_split* sp, const gnn_split* pieces,
-                       bool* pieces_done) {
-  if (a.nrows == 0 || a.F == 0) return GNN_OK;
-  if (sp) return launch_mode_split<MODE>(a, vec, st, sp);
-  if ((a.F <= 4 && (MODE == GNN_AGG_MEAN || MODE == GNN_AGG_MEAN_BWD || MODE == GNN_AGG_SUM)) ||
-      (a.F <= 2 && MODE == GNN_AGG_GCN)) {  // (GCN: the 2-class logits and their transpose, r54)
-    // slots staged per pass: 512 / 128 measured 15.3 / 17.2 us vs 16.1 at 256 (r10, warm)
-    const unsigned nb = (unsigned)ceil_div(a.nrows, 256);
-    // rows longer than 32 slots of a pass: the tail by the whole wave (r17 lab, SAGE preset F = 2:
-    // fwd 14.4 -> 13.2 us, CSC bwd 15.2 -> 14.4 cold); lab 15: each lane walks its whole row
+template <int MODE, int VEC, int LPS, int NCHMAX>
+void launch_flat(const AggArgs& a, int rpg, unsigned blocks, hipStream_t st, [[maybe_unused]] bool prefetch) {
 #ifdef GNNMP_AGG_LAB
-    if (g_agg_lab_variant == 15) {
-      if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, false><<<nb, 256, 0, st>>>(a);
-      else if constexpr (MODE != GNN_AGG_GCN) agg_narrow_lds_kernel<MODE, 4, 256, false><<<nb, 256, 0, st>>>(a);
-    } else
+  if (prefetch) return (void)agg_flat_kernel<MODE, VEC, LPS, NCHMAX, true><<<blocks, 256, 0, st>>>(a, rpg);
 #endif
-    if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, true><<<nb, 256, 0, st>>>(a);
-    else if constexpr (MODE != GNN_AGG_GCN) agg_narrow_lds_kernel<MODE, 4, 256, true><<<nb, 256, 0, st>>>(a);
+  agg_flat_kernel<MODE, VEC, LPS, NCHMAX><<<blocks, 256, 0, st>>>(a, rpg);
+}
+
+// One pass over a.ptr / a.nbr.  fold: the split whose pieces (one wave each) ride in this launch
+// (launch_mode_split decides; 16-lane groups only).
+template <int MODE>
+gnn_status launch_mode(const AggArgs& a, int vec, hipStream_t st, const gnn_split* fold = nullptr) {
+  if (a.nrows == 0 || a.F == 0) return GNN_OK;
+  const AggLab lab = agg_lab();
+  // widest row of the LDS-staged narrow form: SUM / MEAN / MEAN_BWD 4, GCN 2 (the 2-class logits
+  // and their transpose, r54), EDGE_W none; wider rows up to 8 take a lane group per row
+  constexpr int kLdsF = MODE == GNN_AGG_EDGE_W ? 0 : MODE == GNN_AGG_GCN ? 2 : 4;
+  if (a.F <= kLdsF) {
+    if constexpr (kLdsF >= 2) {
+      // slots staged per pass: 512 / 128 measured 15.3 / 17.2 us vs 16.1 at 256 (r10, warm)
+      const unsigned nb = (unsigned)ceil_div(a.nrows, 256);
+      // rows longer than 32 slots of a pass: the tail by the whole wave (r17 lab, SAGE preset F = 2:
+      // fwd 14.4 -> 13.2 us, CSC bwd 15.2 -> 14.4 cold); lab.lane_walk: each lane walks its whole row
+#ifdef GNNMP_AGG_LAB
+      if (lab.lane_walk) {
+        if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, false><<<nb, 256, 0, st>>>(a);
+        else if constexpr (kLdsF >= 4) agg_narrow_lds_kernel<MODE, 4, 256, false><<<nb, 256, 0, st>>>(a);
+      } else
+#endif
+      if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, true><<<nb, 256, 0, st>>>(a);
+      else if constexpr (kLdsF >= 4) agg_narrow_lds_kernel<MODE, 4, 256, true><<<nb, 256, 0, st>>>(a);
+    }
   } else if (a.F <= 8) {
     int64_t blocks = ceil_div(a.nrows * kGroup, 256);
     if (blocks > ((int64_t)1 << 20)) blocks = (int64_t)1 << 20;
-    if (a.F <= 2) agg_group_kernel<MODE, 2><<<(unsigned)blocks, 256, 0, st>>>(a);
-    else if (a.F <= 4) agg_group_kernel<MODE, 4><<<(unsigned)blocks, 256, 0, st>>>(a);
-    else agg_group_kernel<MODE, 8><<<(unsigned)blocks, 256, 0, st>>>(a);
+    if (a.F > 4) agg_group_kernel<MODE, 8><<<(unsigned)blocks, 256, 0, st>>>(a);
+    else if constexpr (kLdsF < 4) {  // (kLdsF < F here)
+      if (a.F > 2) agg_group_kernel<MODE, 4><<<(unsigned)blocks, 256, 0, st>>>(a);
+      else if constexpr (kLdsF < 2) agg_group_kernel<MODE, 2><<<(unsigned)blocks, 256, 0, st>>>(a);
+    }
   } else {
     const int nchunk = a.F / vec;
-    int lps = 64;
-    if (nchunk <= 8) lps = 8;
-    else if (nchunk <= 16) lps = 16;
-    else if (nchunk <= 32) lps = 32;
+    const int lps = flat_lps(nchunk);
     if (nchunk > 64 * 4) return fail(GNN_ERR_UNSUPPORTED, "gnn_aggregate_f32", "F too wide for the gather kernel");
     // rows per group: the group's lanes hold rpg + 1 row pointers, so rpg <= lps - 1.  16-lane
     // groups (F = 64): 2 rows — the 4 groups of a wave walk their rows in lockstep more often and
     // flush (divergently) fewer rows per pass: GCN preset F = 64, CSR fwd with bias / ReLU /
     // dropout 97.5 -> 89.2 us, CSC bwd 49.4 -> 41.3 us (profiles/lab_agg.py, r08; 4 rows: 91.5 /
-    // 41.7, lps - 1 = 15 rows: 116.9 / 48.7).  Lab 5 / 6 / 8: 4 / 8 / lps - 1 rows.
-    const int lv = g_agg_lab_variant;
+    // 41.7, lps - 1 = 15 rows: 116.9 / 48.7).
     // degree-ordered split main pass (a.order): ONE row per group — a wave's groups hold rows of
     // the same length, so they walk in lockstep and nothing is gained by walking several rows
     // flat; more, shorter-lived groups hide more latency (r14 lab, F = 64: SAGE mean fwd 59.7 ->
     // 50.3 us, CSC mean bwd 80.0 -> 62.9, GCN fwd 73.5 -> 59.1; plan order at 2 rows: 71 / 98 / 84)
-    const int rpg = lv == 5 ? 4 : lv == 6 ? 8 : lv == 8 ? lps - 1 : (lv == 9 || lv == 11) ? 1
-                  : a.order ? 1 : (lps == 8 ? 7 : lps == 16 ? 2 : 8);
-    const int64_t groups = ceil_div(a.nrows, rpg);
-    const unsigned blocks = (unsigned)ceil_div(groups * lps, 256);
-    const bool pf = lv == 10 || lv == 11;  // lab: neighbour-id prefetch (r14: 5-10 us slower)
-    // split pieces (one wave each) folded into the main pass's launch: 16-lane groups only (r17:
-    // F = 64 passes 10-12 us faster; at F = 128 (32-lane groups) the scaled config's CSC pass
-    // measured 1463 -> 1679 us, the pieces' registers lowering the main pass's occupancy)
-    const bool fold = pieces && pieces->num_pieces > pieces->num_long && !pf && lps == 16 && lv != 16;
-    const unsigned pblocks = fold ? (unsigned)ceil_div(pieces->num_pieces * 64, 256) : 0u;
-    if (fold && pieces_done) *pieces_done = true;
-#ifdef GNNMP_AGG_LAB
-#define GNN_FLAT_PF(V, L, NC) if (pf) agg_flat_kernel<MODE, V, L, NC, true><<<blocks, 256, 0, st>>>(a, rpg); else
-#else
-#define GNN_FLAT_PF(V, L, NC)
-#endif
-#define GNN_FLAT(V, L, NC)                                                                                 \
-  do {                                                                                                     \
-    GNN_FLAT_PF(V, L, NC)                                                                                  \
-    if (fold)                                                                                              \
-      agg_flat_pieces_kernel<MODE, V, L, NC><<<blocks + pblocks, 256, 0, st>>>(a, rpg, pieces->num_pieces,   \
-                                                                           pieces->piece_seg, pblocks);    \
-    else agg_flat_kernel<MODE, V, L, NC><<<blocks, 256, 0, st>>>(a, rpg);                                    \
-  } while (0)
-#define GNN_FLAT_V(V)                      \
-  do {                                     \
-    if (lps == 64) GNN_FLAT(V, 64, 4);     \
-    else if (lps == 32) GNN_FLAT(V, 32, 1); \
-    else if (lps == 16) GNN_FLAT(V, 16, 1); \
-    else GNN_FLAT(V, 8, 1);                \
-  } while (0)
-    if (lps == 64 && nchunk <= 128) {  // wave-uniform fast path (scalar row/neighbour handling)
-      // 16 rows per wave.  r08 lab (profiles/lab_agg.py, SAGE preset F = 166 CSR, 89.4 us = 63 %
-      // of HBM): 8 rows 89.2, 4 rows 95.7, 32 rows 99.1; U = 4 rows in flight 91.9; a 168-float
-      // padded pitch (dwordx4, one load per row) 89.0 — the gather is not instruction-bound.
-      // XCD-grouped block order (each XCD sweeping one contiguous eighth of the rows) measured
-      // slower with cold caches (r10: 130.4 -> 138.5 us).  Lab 1 / 2 / 3: 8 / 4 / 32 rows.
-      const int rpw = (lv == 1 || lv == 14) ? 8 : (lv == 2 || lv == 13) ? 4 : lv == 3 ? 32 : 16;
-      const unsigned wblocks = (unsigned)ceil_div(ceil_div(a.nrows, rpw) * 64, 256);
-      // (r13 lab: U = 16 neighbour rows in flight instead of 8, 98.5 -> 308.7 us warm — register
-      // pressure; not kept)
-      if (vec == 4) agg_wave_kernel<MODE, 4, 2, false, 8><<<wblocks, 256, 0, st>>>(a, rpw);
-      else if (vec == 2) agg_wave_kernel<MODE, 2, 2, false, 8><<<wblocks, 256, 0, st>>>(a, rpw);
-      else agg_wave_kernel<MODE, 1, 2, false, 8><<<wblocks, 256, 0, st>>>(a, rpw);
-    } else if (vec == 4) GNN_FLAT_V(4);
-    else if (vec == 2) GNN_FLAT_V(2);
-    else GNN_FLAT_V(1);
-#undef GNN_FLAT_V
-#undef GNN_FLAT
-#undef GNN_FLAT_PF
+    const int rpg = lab.rpg > 0 ? lab.rpg : lab.rpg < 0 ? lps - 1 : a.order ? 1 : (lps == 8 ? 7 : lps == 16 ? 2 : 8);
+    const unsigned blocks = (unsigned)ceil_div(ceil_div(a.nrows, rpg) * lps, 256);
+    const unsigned wblocks = (unsigned)ceil_div(ceil_div(a.nrows, lab.rpw) * 64, 256);
+    with_vec(vec, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      // 33 <= nchunk <= 128: the wave-uniform fast path (scalar row/neighbour handling).  (r13 lab: U = 16
+      // neighbour rows in flight instead of 8, 98.5 -> 308.7 us warm — register pressure; not kept)
+      if (lps == 64 && nchunk <= 128) agg_wave_kernel<MODE, V, 2, false, 8><<<wblocks, 256, 0, st>>>(a, lab.rpw);
+      else if (lps == 64) launch_flat<MODE, V, 64, 4>(a, rpg, blocks, st, lab.prefetch);
+      else if (lps == 32) launch_flat<MODE, V, 32, 1>(a, rpg, blocks, st, lab.prefetch);
+      else if (lps == 16 && !fold) launch_flat<MODE, V, 16, 1>(a, rpg, blocks, st, lab.prefetch);
+      else if (lps == 8) {  // (8 < F <= 8 * vec needs vec > 1)
+        if constexpr (V > 1) launch_flat<MODE, V, 8, 1>(a, rpg, blocks, st, lab.prefetch);
+      } else if constexpr (MODE != GNN_AGG_EDGE_W) {  // lps == 16 with the split's pieces (EDGE_W is never split)
+        const unsigned pblocks = (unsigned)ceil_div(fold->num_pieces * 64, 256);
+        agg_flat_pieces_kernel<MODE, V, 16, 1><<<blocks + pblocks, 256, 0, st>>>(a, rpg, fold->num_pieces,
+                                                                               fold->piece_seg, pblocks);
+      }
+    });
   }
   return hip_check(hipGetLastError(), "gnn_aggregate_f32");
+}
+
+// The long-segment split (never EDGE_W): the main pass over the truncated segments (a.ptr / a.nbr
+// are sp's), then pieces 1.. of every long segment, then the ordered combine; F / vec <= 32 in
+// libgnnmp.so, so one wave and one lane chunk (NCH = 1) per piece and per combined row.  (r12: 16- /
+// 32-lane groups, 4 / 2 per wave, measured 6 us slower per F = 64 pass — per-lane id loads and
+// divergent piece lengths)
+template <int MODE>
+gnn_status launch_mode_split(const AggArgs& a, int vec, hipStream_t st, const gnn_split* sp) {
+  if (a.nrows == 0 || a.F == 0) return GNN_OK;
+  const AggLab lab = agg_lab();
+  const bool pieces = sp->num_pieces > sp->num_long;
+  // the pieces folded into the main pass's launch: 16-lane groups only (r17: F = 64 passes 10-12 us
+  // faster; at F = 128 (32-lane groups) the scaled config's CSC pass measured 1463 -> 1679 us,
+  // the pieces' registers lowering the main pass's occupancy)
+  const bool fold = pieces && flat_lps(a.F / vec) == 16 && !lab.prefetch && !lab.no_fold;
+  const gnn_status s = launch_mode<MODE>(a, vec, st, fold ? sp : nullptr);
+  if (s != GNN_OK || sp->num_long == 0) return s;
+  const unsigned pblocks = (unsigned)ceil_div(sp->num_pieces * 64, 256);
+  const unsigned cblocks = (unsigned)ceil_div(sp->num_long * 64, 256);
+  with_vec(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+#ifdef GNNMP_AGG_LAB
+    if (a.F / V > 64) {  // lab.wave_split only: two lane chunks per row
+      if (pieces) agg_piece_wide_kernel<MODE, V, 2><<<pblocks, 256, 0, st>>>(a, sp->num_pieces, sp->piece_seg);
+      return (void)agg_combine_kernel<MODE, V, 2><<<cblocks, 256, 0, st>>>(a, sp->num_long, sp->long_seg);
+    }
+#endif
+    if (pieces && !fold) agg_piece_wide_kernel<MODE, V, 1><<<pblocks, 256, 0, st>>>(a, sp->num_pieces, sp->piece_seg);
+    agg_combine_kernel<MODE, V, 1><<<cblocks, 256, 0, st>>>(a, sp->num_long, sp->long_seg);
+  });
+  return hip_check(hipGetLastError(), fold ? "gnn_aggregate_f32 (split combine)" : "gnn_aggregate_f32 (split passes)");
 }
 
 // ------------------------------------------------------------------ colsum
@@ -1537,6 +1501,27 @@ using namespace gnnmp;
 extern "C" void gnnx_set_agg_variant(int v) { g_agg_lab_variant = v; }
 #endif
 
+// What gnn_aggregate_f32 and gnn_aggregate_bf16 fill alike: the plan arrays of the direction,
+// nodew, addend, bias, ReLU, the dropout (checked) and the shape.
+static gnn_status agg_args_common(AggArgs& a, const gnn_graph* g, const gnn_agg_params* p, int64_t F, const char* fn) {
+  a.ptr = p->transpose ? g->colptr : g->rowptr;
+  a.nbr = p->transpose ? g->row : g->col;
+  a.nodew = p->nodew;
+  a.add = p->addend; a.ld_add = p->ld_add;
+  a.bias = p->bias; a.relu = p->relu;
+  if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return fail(GNN_ERR_INVALID_ARG, fn, "dropout p in [0,1)");
+  if (p->dropout_p > 0.f && (int64_t)g->num_nodes * (int64_t)F >= ((int64_t)1 << 32))
+    return fail(GNN_ERR_UNSUPPORTED, fn, "dropout element index (rows x width) must be < 2^32");
+  a.dropout = p->dropout_p > 0.f;
+  a.keep_thresh = (uint32_t)((1.0 - (double)p->dropout_p) * 16777216.0);
+  a.drop_scale = a.dropout ? (float)(1.0 / (1.0 - (double)p->dropout_p)) : 1.0f;
+  a.seed = p->seed;
+  a.seed_ptr = p->seed_ptr;
+  a.nrows = g->num_nodes;
+  a.F = (int32_t)F;
+  return GNN_OK;
+}
+
 extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params* p, const float* x,
                                         int64_t ldx, int64_t F, float* y, int64_t ldy,
                                         gnn_stream_t stream) {
@@ -1547,26 +1532,12 @@ extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params
   if (p->addend && p->ld_add < F) return fail(GNN_ERR_INVALID_ARG, __func__, "bad ld_add");
   if (p->addend2 && p->ld_add2 < F) return fail(GNN_ERR_INVALID_ARG, __func__, "bad ld_add2");
   AggArgs a{};
-  a.ptr = p->transpose ? g->colptr : g->rowptr;
-  a.nbr = p->transpose ? g->row : g->col;
+  if (const gnn_status s = agg_args_common(a, g, p, F, __func__); s != GNN_OK) return s;
   a.wslot = (p->mode == GNN_AGG_EDGE_W && p->transpose) ? g->csc2csr : nullptr;
-  a.nodew = p->nodew;
   a.ew = p->ew;
   a.heads = p->heads > 0 ? p->heads : 1;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy;
-  a.add = p->addend; a.ld_add = p->ld_add;
   a.add2 = p->addend2; a.ld_add2 = p->ld_add2;
-  a.bias = p->bias; a.relu = p->relu;
-  if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout p in [0,1)");
-  if (p->dropout_p > 0.f && (int64_t)g->num_nodes * (int64_t)F >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
-  a.dropout = p->dropout_p > 0.f;
-  a.keep_thresh = (uint32_t)((1.0 - (double)p->dropout_p) * 16777216.0);
-  a.drop_scale = a.dropout ? (float)(1.0 / (1.0 - (double)p->dropout_p)) : 1.0f;
-  a.seed = p->seed;
-  a.seed_ptr = p->seed_ptr;
-  a.nrows = g->num_nodes;
-  a.F = (int32_t)F;
   if (!a.ptr || (g->num_slots > 0 && !a.nbr)) return fail(GNN_ERR_INVALID_ARG, __func__, "plan arrays null");
   if ((p->mode == GNN_AGG_MEAN || p->mode == GNN_AGG_MEAN_BWD || p->mode == GNN_AGG_GCN) && !p->nodew)
     return fail(GNN_ERR_INVALID_ARG, __func__, "mode needs nodew");
@@ -1605,9 +1576,8 @@ extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params
   // The split pays only for the lane-group gather (8..32 lanes per row, one row at a time per
   // group): r01 measurements — F=64 GCN fwd 72 -> 37 µs; the wave-wide gather (F/vec > 32) and
   // the narrow LDS/group kernels lose to the two extra launches.
-  // (lab 12 / 13 / 14: the split, degree-ordered, for the wave-wide gather too, 16 / 4 / 8 rows per wave)
-  const bool lab_wsplit = g_agg_lab_variant >= 12 && g_agg_lab_variant <= 14;
-  if (sp && (F <= 8 || (F / vec > 32 && !lab_wsplit) || g_agg_lab_variant == 7)) sp = nullptr;  // lab 7: no split
+  const AggLab lab = agg_lab();
+  if (sp && (F <= 8 || F / vec > (lab.wave_split ? 128 : 32) || lab.no_split)) sp = nullptr;
   if (!sp) {
     a.ptr = p->transpose ? g->colptr : g->rowptr;
     a.nbr = p->transpose ? g->row : g->col;
@@ -1617,11 +1587,12 @@ extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params
   }
   hipStream_t st = (hipStream_t)stream;
   switch (p->mode) {
-    case GNN_AGG_SUM: return launch_mode<GNN_AGG_SUM>(a, vec, st, sp);
-    case GNN_AGG_MEAN: return launch_mode<GNN_AGG_MEAN>(a, vec, st, sp);
-    case GNN_AGG_MEAN_BWD: return launch_mode<GNN_AGG_MEAN_BWD>(a, vec, st, sp);
-    case GNN_AGG_GCN: return launch_mode<GNN_AGG_GCN>(a, vec, st, sp);
-    case GNN_AGG_EDGE_W: return launch_mode<GNN_AGG_EDGE_W>(a, vec, st, nullptr);
+    case GNN_AGG_SUM: return sp ? launch_mode_split<GNN_AGG_SUM>(a, vec, st, sp) : launch_mode<GNN_AGG_SUM>(a, vec, st);
+    case GNN_AGG_MEAN: return sp ? launch_mode_split<GNN_AGG_MEAN>(a, vec, st, sp) : launch_mode<GNN_AGG_MEAN>(a, vec, st);
+    case GNN_AGG_MEAN_BWD:
+      return sp ? launch_mode_split<GNN_AGG_MEAN_BWD>(a, vec, st, sp) : launch_mode<GNN_AGG_MEAN_BWD>(a, vec, st);
+    case GNN_AGG_GCN: return sp ? launch_mode_split<GNN_AGG_GCN>(a, vec, st, sp) : launch_mode<GNN_AGG_GCN>(a, vec, st);
+    case GNN_AGG_EDGE_W: return launch_mode<GNN_AGG_EDGE_W>(a, vec, st);  // (sp is null: never split)
   }
   return fail(GNN_ERR_INVALID_ARG, __func__, "unknown mode");
 }
@@ -1661,15 +1632,11 @@ gnn_status launch_bf16(const AggArgs& a, int vec, bool vec8, hipStream_t st) {
       return hip_check(hipGetLastError(), "gnn_aggregate_bf16");
     }
   }
-  if (nchunk <= 64) {
-    if (vec == 4) agg_wave_kernel<MODE, 4, 1, true><<<wblocks, 256, 0, st>>>(a, rpw);
-    else if (vec == 2) agg_wave_kernel<MODE, 2, 1, true><<<wblocks, 256, 0, st>>>(a, rpw);
-    else agg_wave_kernel<MODE, 1, 1, true><<<wblocks, 256, 0, st>>>(a, rpw);
-  } else {
-    if (vec == 4) agg_wave_kernel<MODE, 4, 2, true><<<wblocks, 256, 0, st>>>(a, rpw);
-    else if (vec == 2) agg_wave_kernel<MODE, 2, 2, true><<<wblocks, 256, 0, st>>>(a, rpw);
-    else agg_wave_kernel<MODE, 1, 2, true><<<wblocks, 256, 0, st>>>(a, rpw);
-  }
+  with_vec(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    if (nchunk <= 64) agg_wave_kernel<MODE, V, 1, true><<<wblocks, 256, 0, st>>>(a, rpw);
+    else agg_wave_kernel<MODE, V, 2, true><<<wblocks, 256, 0, st>>>(a, rpw);
+  });
   return hip_check(hipGetLastError(), "gnn_aggregate_bf16");
 }
 
@@ -1686,27 +1653,14 @@ extern "C" gnn_status gnn_aggregate_bf16(const gnn_graph* g, const gnn_agg_param
   if (g->num_nodes > 0 && F > 0 && (!x || !y)) return fail(GNN_ERR_INVALID_ARG, __func__, "null x/y");
   if (p->addend && p->ld_add < F) return fail(GNN_ERR_INVALID_ARG, __func__, "bad ld_add");
   if (p->addend2) return fail(GNN_ERR_UNSUPPORTED, __func__, "addend2 is f32-only");
+  if (!(p->transpose ? g->colptr : g->rowptr) || (g->num_slots > 0 && !(p->transpose ? g->row : g->col)))
+    return fail(GNN_ERR_INVALID_ARG, __func__, "plan arrays null");
   AggArgs a{};
-  a.ptr = p->transpose ? g->colptr : g->rowptr;
-  a.nbr = p->transpose ? g->row : g->col;
-  if (!a.ptr || (g->num_slots > 0 && !a.nbr)) return fail(GNN_ERR_INVALID_ARG, __func__, "plan arrays null");
-  a.nodew = p->nodew;
+  if (const gnn_status s = agg_args_common(a, g, p, F, __func__); s != GNN_OK) return s;
   a.heads = 1;
   a.chan = (int32_t)(F > 0 ? F : 1);
   a.x = static_cast<const float*>(x); a.ldx = ldx;
   a.y = static_cast<float*>(y); a.ldy = ldy;
-  a.add = p->addend; a.ld_add = p->ld_add;
-  a.bias = p->bias; a.relu = p->relu;
-  if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout p in [0,1)");
-  if (p->dropout_p > 0.f && (int64_t)g->num_nodes * (int64_t)F >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
-  a.dropout = p->dropout_p > 0.f;
-  a.keep_thresh = (uint32_t)((1.0 - (double)p->dropout_p) * 16777216.0);
-  a.drop_scale = a.dropout ? (float)(1.0 / (1.0 - (double)p->dropout_p)) : 1.0f;
-  a.seed = p->seed;
-  a.seed_ptr = p->seed_ptr;
-  a.nrows = g->num_nodes;
-  a.F = (int32_t)F;
   auto ok_vec = [&](int v) {
     if (F % v || ldx % v || ldy % v || (p->addend && p->ld_add % v)) return false;
     return aligned(x, 2 * v) && aligned(y, 2 * v) && aligned(p->addend, 4 * v);
@@ -1779,11 +1733,10 @@ static gnn_status sage_mean_fwd_image(const gnn_graph* g, const float* deg, cons
     if (s != GNN_OK) return s;
     a.hp.gblocks = BN / 4;  // one wave per output column (ws_prep_h2_cols<256>)
   }
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
   const bool v4 = F % 4 == 0 && ldx % 4 == 0 && width % 4 == 0 && ld % 4 == 0 && plane_stride % 4 == 0 &&
-                  al(x, 16) && al(img, 8);
+                  aligned(x, 16) && aligned(img, 8);
   const bool v2 = F % 2 == 0 && ldx % 2 == 0 && width % 2 == 0 && ld % 2 == 0 && plane_stride % 2 == 0 &&
-                  al(x, 8) && al(img, 4);
+                  aligned(x, 8) && aligned(img, 4);
   const int vec = v4 ? 4 : 2;
   if (!v2 || F / vec <= 32 || ceil_div(width, vec) > 128)
     return fail(GNN_ERR_UNSUPPORTED, fn, "needs even F, 32 < F / vec, width / vec <= 128 and aligned rows");
@@ -1805,10 +1758,14 @@ static gnn_status sage_mean_fwd_image(const gnn_graph* g, const float* deg, cons
   const int64_t nwaves = a.wstart ? hub->num_pieces : ceil_div(a.nrows, 16);
   const unsigned wblocks = (unsigned)ceil_div(nwaves * 64, 256) + (unsigned)a.hp.gblocks + (unsigned)a.nhub;
   hipStream_t st = (hipStream_t)stream;
-  if (vec == 4 && ceil_div(width, 4) <= 64)  // one pass per row (e.g. a 168-wide padded x: 42 lanes)
-    agg_wave_kernel<GNN_AGG_MEAN, 4, 1, false, 8, PLN><<<wblocks, 256, 0, st>>>(a, rpw);
-  else if (vec == 4) agg_wave_kernel<GNN_AGG_MEAN, 4, 2, false, 8, PLN><<<wblocks, 256, 0, st>>>(a, rpw);
-  else agg_wave_kernel<GNN_AGG_MEAN, 2, 2, false, 8, PLN><<<wblocks, 256, 0, st>>>(a, rpw);
+  with_vec(vec, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    if constexpr (V == 4) {
+      if (ceil_div(width, 4) <= 64)  // one pass per row (e.g. a 168-wide padded x: 42 lanes)
+        return (void)agg_wave_kernel<GNN_AGG_MEAN, 4, 1, false, 8, PLN><<<wblocks, 256, 0, st>>>(a, rpw);
+    }
+    if constexpr (V > 1) agg_wave_kernel<GNN_AGG_MEAN, V, 2, false, 8, PLN><<<wblocks, 256, 0, st>>>(a, rpw);  // (vec is 4 or 2)
+  });
   return hip_check(hipGetLastError(), fn);
 }
 

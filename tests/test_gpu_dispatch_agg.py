@@ -15,7 +15,7 @@ The dispatcher (aggregate.hip, gnn_aggregate_f32 -> launch_mode / launch_mode_sp
              main pass agg_flat_kernel<V, 8|32, 1> over the truncated segments in degree order,
              agg_piece_wide_kernel<V, 1> and agg_combine_kernel<V, 1>; 16-lane groups take the
              pieces into the main pass's launch (agg_flat_pieces_kernel<V, 16, 1>) + the combine.
-agg_flat_kernel<*, 1, 8, 1> cannot be reached (F > 8 at vec 1 is nchunk >= 9), nor can the split's
+agg_flat_kernel<*, 1, 8, 1> is not instantiated (F > 8 at vec 1 is nchunk >= 9), nor are the split's
 NCH = 2 / 4 piece and combine forms (the split runs only for nchunk <= 32).
 
 KERNEL and CASES below are that reading written out: the kernels each (F, vec) must select, unsplit
