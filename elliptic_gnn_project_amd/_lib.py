@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -154,6 +154,12 @@ class GnnGemmTNParams(ctypes.Structure):
 
 
 ROWMAX_ROWS = 16  # GNN_ROWMAX_ROWS (ABI 25)
+ACTIVE_ROWS = 16  # GNN_ACTIVE_ROWS (ABI 28)
+
+
+class GnnAggActive(ctypes.Structure):
+    """gnn_agg_active (ABI 28): the activity flags an aggregation writes for its output's row groups."""
+    _fields_ = [("row_active", c_ptr), ("active_with", c_ptr), ("ld_active_with", c_i64), ("active_with_cols", c_i32)]
 
 
 # gnn_act
@@ -230,6 +236,11 @@ SIGNATURES = {
     "gnn_aggregate_f32": (
         ctypes.c_int,
         [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnAggParams), c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr],
+    ),
+    "gnn_aggregate_active_f32": (
+        ctypes.c_int,
+        [ctypes.POINTER(GnnGraph), ctypes.POINTER(GnnAggParams), c_ptr, c_i64, c_i64, c_ptr, c_i64,
+         ctypes.POINTER(GnnAggActive), c_ptr],
     ),
     "gnn_aggregate_bf16": (
         ctypes.c_int,
@@ -312,6 +323,8 @@ SIGNATURES = {
     "gnn_gemm_tn_workspace_size": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i32, ctypes.POINTER(c_size)]),
     "gnn_gemm_tn_sq_blocks": (ctypes.c_int, [c_i64, ctypes.POINTER(c_i32)]),
     "gnn_gemm_tn_f32": (ctypes.c_int, [ctypes.POINTER(GnnGemmTNParams), c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_gemm_tn_active_f32": (ctypes.c_int, [ctypes.POINTER(GnnGemmTNParams), c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_gemm_tn_active_pays": (ctypes.c_int, [c_i64]),
     "gnn_gemm_nt_planes_ok": (ctypes.c_int, [ctypes.POINTER(GnnGemmNTParams)]),
     "gnn_gemm_nt_colsum_blocks": (ctypes.c_int, [ctypes.POINTER(GnnGemmNTParams), ctypes.POINTER(c_i32)]),
     "gnn_colsum_finish_f32": (ctypes.c_int, [c_ptr, c_i32, c_i64, c_ptr, c_ptr]),

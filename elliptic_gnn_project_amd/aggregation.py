@@ -93,11 +93,17 @@ def aggregate(plan: GraphPlan, x: torch.Tensor, mode: int, transpose: bool = Fal
               nodew: torch.Tensor | None = None, ew: torch.Tensor | None = None, heads: int = 1,
               addend: torch.Tensor | None = None, bias: torch.Tensor | None = None,
               relu: bool = False, out: torch.Tensor | None = None, dropout_p: float = 0.0, seed: int = 0,
-              seed_ptr: torch.Tensor | None = None, addend2: torch.Tensor | None = None) -> torch.Tensor:
+              seed_ptr: torch.Tensor | None = None, addend2: torch.Tensor | None = None,
+              active: tuple | None = None) -> torch.Tensor:
     """Raw call of gnn_aggregate_f32 (no autograd); bf16 rows go to gnn_aggregate_bf16 (bf16 out).
     ``dropout_p`` > 0: counter-hash dropout of element r·F + f after bias / ReLU (fp32 path).
-    ``addend2``: a second [N, F] term summed after ``addend`` (fp32 path, ABI 20)."""
+    ``addend2``: a second [N, F] term summed after ``addend`` (fp32 path, ABI 20).
+    ``active`` = (flags, with_): the launch also writes the uint8 flags [ceil(N / 16)] of the output's
+    16-row groups — nonzero iff a row of the group has a nonzero output or a nonzero in ``with_``
+    ([N, <= 4] f32 or None); gnn_aggregate_active_f32 (ABI 28), the narrow F <= 4 form only."""
     if x.dtype == torch.bfloat16:
+        if active is not None:
+            raise NotImplementedError("activity flags on the bf16-storage aggregation")
         if dropout_p > 0 or addend2 is not None:
             raise NotImplementedError("dropout / addend2 epilogue on the bf16-storage aggregation")
         return _aggregate_bf16(plan, x, mode, transpose, nodew, addend, bias, relu, out)
@@ -126,8 +132,19 @@ def aggregate(plan: GraphPlan, x: torch.Tensor, mode: int, transpose: bool = Fal
         a = torch.cuda.Event(enable_timing=True)
         b = torch.cuda.Event(enable_timing=True)
         a.record()
-    _lib.call("gnn_aggregate_f32", plan.c_graph, p, x.data_ptr(), _ld(x), F, out.data_ptr(), _ld(out),
-              _lib.stream_handle(x.device))
+    if active is not None:
+        flags, with_ = active
+        if flags.dtype != torch.uint8 or flags.numel() < (N + _lib.ACTIVE_ROWS - 1) // _lib.ACTIVE_ROWS:
+            raise ValueError("activity flags: uint8, one per 16 rows")
+        if with_ is not None and (with_.dtype != torch.float32 or with_.size(0) != N or with_.stride(1) != 1):
+            raise ValueError("active with_: f32 rows of the plan's nodes")
+        act = _lib.GnnAggActive(flags.data_ptr(), _lib.ptr(with_), _ld(with_) if with_ is not None else 0,
+                                with_.size(1) if with_ is not None else 0)
+        _lib.call("gnn_aggregate_active_f32", plan.c_graph, p, x.data_ptr(), _ld(x), F, out.data_ptr(), _ld(out),
+                  act, _lib.stream_handle(x.device))
+    else:
+        _lib.call("gnn_aggregate_f32", plan.c_graph, p, x.data_ptr(), _ld(x), F, out.data_ptr(), _ld(out),
+                  _lib.stream_handle(x.device))
     if KernelTimer.active:
         b.record()
         KernelTimer.records.append((("agg", int(mode), bool(transpose), int(F)), a, b,

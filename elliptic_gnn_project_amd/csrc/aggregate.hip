@@ -110,6 +110,9 @@ struct AggArgs {
   // long-segment split (gnn_split): main pass over truncated segments writes raw partials of
   // long segments to part[piece0[r]]; pieces / combine passes read the full segments
   const int32_t* piece0;   // null: no split
+  // (ABI 28, gnn_agg_active) the narrow LDS form: one byte per GNN_ACTIVE_ROWS output rows, nonzero iff
+  // some row of the group has a nonzero among its F outputs or act_with[r, 0:act_cols]
+  uint8_t* row_active; const float* act_with; int64_t ld_act_with; int32_t act_cols;
   const int32_t* order;    // split main pass in degree order: position -> row (null: identity)
   float* part;
   const int32_t* fptr;
@@ -966,8 +969,14 @@ __global__ __launch_bounds__(256) void agg_group_kernel(AggArgs a) {
 // then stay for the block's one barrier instead of returning.
 // CEV: the CE of a gnn_ce_spec with row weights or focal (masked_ce_row<4, true>); the plain CE
 // instantiations are untouched by it.
-template <int MODE, int NF, int kNarrowCap = 256, bool COOP = false, bool CE = false, bool CEV = false>  // kNarrowCap: slots staged per pass per wave
+// ACT (ABI 28): the wave's 64 rows are four GNN_ACTIVE_ROWS groups — one ballot of "my row's output
+// or its act_with columns hold a nonzero" gives the wave its four flag bytes, stored as one word
+// (byte by byte where the array ends inside the word).  A row a later pass finishes (piece0 >= 0)
+// counts as nonzero.  The instantiations without it are untouched.
+template <int MODE, int NF, int kNarrowCap = 256, bool COOP = false, bool CE = false, bool CEV = false,
+          bool ACT = false>  // kNarrowCap: slots staged per pass per wave
 __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
+  static_assert(!ACT || (!CE && GNN_ACTIVE_ROWS == 16), "ACT: the plain aggregation, 16-row groups");
   __shared__ float sv[4][kNarrowCap * 4];
   const int lane = threadIdx.x & 63;
   const int w = threadIdx.x >> 6;
@@ -1023,6 +1032,12 @@ __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
     if constexpr (CEV) {
       if (a.ce_rw) ce_rw = a.ce_rw[rr];
     }
+  }
+  float actv[4] = {0.f, 0.f, 0.f, 0.f};  // ACT: the row's act_with columns (clamped, no branch around a load)
+  if constexpr (ACT) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (a.act_cols > 0) actv[c] = a.act_with[rr * a.ld_act_with + min(c, a.act_cols - 1)];
   }
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
   float* buf = sv[w];
@@ -1125,6 +1140,26 @@ __global__ __launch_bounds__(256) void agg_narrow_lds_kernel(AggArgs a) {
           a.y[r * a.ldy + f] = t[0];
           lg[f] = t[0];
         }
+      }
+    }
+  }
+  if constexpr (ACT) {  // (every lane of the wave is here: r0 < nrows is wave-uniform)
+    bool nz = false;
+    if (rok) {
+      nz = a.piece0 && a.piece0[r] >= 0;
+#pragma unroll
+      for (int f = 0; f < 4; ++f) nz = nz || (f < F && lg[f] != 0.0f) || (f < a.act_cols && actv[f] != 0.0f);
+    }
+    const uint64_t bm = __ballot(nz);
+    uint32_t word = 0u;
+#pragma unroll
+    for (int gq = 0; gq < 4; ++gq) word |= ((bm >> (16 * gq)) & 0xffffu) ? (1u << (8 * gq)) : 0u;
+    const int64_t g0 = r0 / GNN_ACTIVE_ROWS, ng = (a.nrows + GNN_ACTIVE_ROWS - 1) / GNN_ACTIVE_ROWS;
+    if (lane == 0) {
+      if (g0 + 4 <= ng) {
+        *reinterpret_cast<uint32_t*>(a.row_active + g0) = word;  // (4-byte aligned: g0 % 4 == 0)
+      } else {
+        for (int gq = 0; g0 + gq < ng; ++gq) a.row_active[g0 + gq] = (uint8_t)((word >> (8 * gq)) & 0xffu);
       }
     }
   }
@@ -1347,6 +1382,10 @@ gnn_status launch_mode(const AggArgs& a, int vec, hipStream_t st, const gnn_spli
         else if constexpr (kLdsF >= 4) agg_narrow_lds_kernel<MODE, 4, 256, false><<<nb, 256, 0, st>>>(a);
       } else
 #endif
+      if (a.row_active) {  // (ABI 28) the same kernels, also writing the row groups' activity flags
+        if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, true, false, false, true><<<nb, 256, 0, st>>>(a);
+        else if constexpr (kLdsF >= 4) agg_narrow_lds_kernel<MODE, 4, 256, true, false, false, true><<<nb, 256, 0, st>>>(a);
+      } else
       if (a.F <= 2) agg_narrow_lds_kernel<MODE, 2, 256, true><<<nb, 256, 0, st>>>(a);
       else if constexpr (kLdsF >= 4) agg_narrow_lds_kernel<MODE, 4, 256, true><<<nb, 256, 0, st>>>(a);
     }
@@ -1525,7 +1564,22 @@ static gnn_status agg_args_common(AggArgs& a, const gnn_graph* g, const gnn_agg_
 extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params* p, const float* x,
                                         int64_t ldx, int64_t F, float* y, int64_t ldy,
                                         gnn_stream_t stream) {
+  return gnn_aggregate_active_f32(g, p, x, ldx, F, y, ldy, nullptr, stream);
+}
+
+extern "C" gnn_status gnn_aggregate_active_f32(const gnn_graph* g, const gnn_agg_params* p, const float* x,
+                                               int64_t ldx, int64_t F, float* y, int64_t ldy,
+                                               const gnn_agg_active* act, gnn_stream_t stream) {
   if (!g || !p) return fail(GNN_ERR_INVALID_ARG, __func__, "null graph or params");
+  if (act && !act->row_active) act = nullptr;
+  if (act) {  // (ABI 28) only the narrow LDS form writes flags: refused here, before any launch
+    if (act->active_with_cols < 0 || act->active_with_cols > 4 || (act->active_with_cols > 0 && !act->active_with) ||
+        act->ld_active_with < act->active_with_cols || (reinterpret_cast<uintptr_t>(act->row_active) & 3))
+      return fail(GNN_ERR_INVALID_ARG, __func__, "activity flags: 0 <= active_with_cols <= 4, ld >= cols, 4-byte aligned flags");
+    const int64_t fmax = p->mode == GNN_AGG_EDGE_W ? 0 : p->mode == GNN_AGG_GCN ? 2 : 4;
+    if (F < 1 || F > fmax || agg_lab().lane_walk)
+      return fail(GNN_ERR_UNSUPPORTED, __func__, "activity flags need the narrow form (F <= 4; GCN F <= 2; not EDGE_W)");
+  }
   if (F < 0 || F > INT32_MAX || ldx < F || ldy < F)
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad F / leading dimensions");
   if (g->num_nodes > 0 && F > 0 && (!x || !y)) return fail(GNN_ERR_INVALID_ARG, __func__, "null x/y");
@@ -1538,6 +1592,10 @@ extern "C" gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params
   a.heads = p->heads > 0 ? p->heads : 1;
   a.x = x; a.ldx = ldx; a.y = y; a.ldy = ldy;
   a.add2 = p->addend2; a.ld_add2 = p->ld_add2;
+  if (act) {
+    a.row_active = act->row_active; a.act_with = act->active_with;
+    a.ld_act_with = act->ld_active_with; a.act_cols = act->active_with_cols;
+  }
   if (!a.ptr || (g->num_slots > 0 && !a.nbr)) return fail(GNN_ERR_INVALID_ARG, __func__, "plan arrays null");
   if ((p->mode == GNN_AGG_MEAN || p->mode == GNN_AGG_MEAN_BWD || p->mode == GNN_AGG_GCN) && !p->nodew)
     return fail(GNN_ERR_INVALID_ARG, __func__, "mode needs nodew");

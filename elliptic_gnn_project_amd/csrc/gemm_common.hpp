@@ -193,7 +193,13 @@ struct TNArgs {
   const uint32_t* growmax;  // (ABI 25) the g form's max |G| per GNN_ROWMAX_ROWS rows (float bits), or null
   // (ABI 26) the half-pair dz form: dz[:, 0:ccols] formed in the TN as the CSC sum of u (null: read)
   const int32_t* cptr; const int32_t* cnbr; const float* cu; int64_t ldu; int32_t ccols;
+  // (ABI 28) the half-pair dz form: one byte per GNN_ACTIVE_ROWS rows of dz, 0 = the group's dz rows
+  // are all zero (each block walks only the flagged chunks of its row block); null: every chunk
+  const uint8_t* dz_active;
 };
+// the most 16-row chunks a row block of the flag-driven TN holds (tn_h2_ok bounds M below 1.6 M
+// rows: 2 · ceil(ceil(M / 32) / 256) <= 392); at most one per thread of its 512
+constexpr int TN_ACT_CAP = 512;
 
 // split-bf16 ("x3": each f32 operand = hi + mid + lo bf16, 6 MFMA products) launchers,
 // defined in gemm_x3.hip.  Only the w1/w2 (in-place Linear weight) B form runs split.

@@ -796,6 +796,16 @@ static bool tn_csc_in_kernel(int64_t rows_per_block) {
   return (rows_per_block + 63) / 64 + 1 <= 8;  // groups a block's rows can touch <= its waves
 }
 
+// (ABI 28) whether the dz-form TN at M rows walks activity flags: its row block is larger than the
+// in-kernel CSC fold takes (tn_csc_in_kernel's shape rule, without the env override: a rule of M
+// alone, so the caller's CSC sum, the call-side one and GNNMP_TN_CSC=0 all reach the same kernel)
+static bool tn_active_pays(int64_t M) {
+  if (M < 16) return false;
+  const int64_t rpb = tn_h2_rows_per_block(M, true);
+  return (rpb + 63) / 64 + 1 > 8;
+}
+static int64_t tn_active_bytes(int64_t M) { return (ceil_div(M, GNN_ACTIVE_ROWS) + 15) / 16 * 16; }
+
 // the in-kernel half-pair TN at Nr <= 64, k1 + k2 <= 128 holds three blocks per CU (its LDS is
 // sized by its k-tiles and 64 G rows, 47 KB): three times the blocks, so three times the chunk loads
 // in flight per CU (its chunk loop is latency-bound: one 16-row chunk in flight per block)
@@ -972,11 +982,15 @@ extern "C" gnn_status gnn_gemm_tn_workspace_size(int64_t M, int64_t Nr, int64_t 
   if (Nr <= 8 && nproj == 0) nb = std::max<int64_t>(nb, tn_skinny_blocks(M));  // gemm_skinny.hip
   if (Nr <= 64 && Kc <= 128 && nproj == 0) nb = std::max<int64_t>(nb, tn_blocks2(M));  // the narrow half-pair TN
   *bytes = (size_t)nb * stride * sizeof(float);
+  // (ABI 28) the call-side CSC sum's activity flags, past the slabs of tn_blocks(M) blocks
+  if (nproj > 0 && tn_active_pays(M)) *bytes += (size_t)tn_active_bytes(M);
   return GNN_OK;
 }
 
+extern "C" int gnn_gemm_tn_active_pays(int64_t M) { return tn_active_pays(M) ? 1 : 0; }
+
 static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* workspace,
-                                   size_t workspace_bytes, gnn_stream_t stream);
+                                   size_t workspace_bytes, gnn_stream_t stream, const uint8_t* dz_active = nullptr);
 
 // (ABI 26) the folded CSC sum's arguments (dz_graph's CSC, dz_u, dz_cols); false when dz_graph is
 // given but cannot be taken (no dz form, no u, dz_cols outside 1..min(2, nproj), num_nodes != M)
@@ -1004,11 +1018,24 @@ extern "C" gnn_status gnn_gemm_tn_f32(const gnn_gemm_tn_params* p, float* out, v
   return gemm_tn_dispatch(p, out, workspace, workspace_bytes, stream);
 }
 
+extern "C" gnn_status gnn_gemm_tn_active_f32(const gnn_gemm_tn_params* p, const uint8_t* dz_active, float* out,
+                                             void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
+  return gemm_tn_dispatch(p, out, workspace, workspace_bytes, stream, dz_active);
+}
+
 
 static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* workspace,
-                                   size_t workspace_bytes, gnn_stream_t stream) {
-  const char* __fn = "gnn_gemm_tn_f32";
+                                   size_t workspace_bytes, gnn_stream_t stream, const uint8_t* dz_active) {
+  const char* __fn = dz_active ? "gnn_gemm_tn_active_f32" : "gnn_gemm_tn_f32";
   if (!p || !out) return fail(GNN_ERR_INVALID_ARG, __fn, "null params/out");
+  // (ABI 28) flags: the half-pair dz form with h, no gout, no dz_graph (checked again with the
+  // image's shape below) — refused here, before any launch
+  if (dz_active) {
+    if (!p->dz || !p->h || p->gout || p->dz_graph || !p->a_planes || p->planes_format != GNN_PLANES_HALF_PAIR ||
+        p->math == GNN_MATH_F32 || p->M < 16)
+      return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active needs the half-pair dz form with h, no gout, no dz_graph, M >= 16");
+    if (reinterpret_cast<uintptr_t>(dz_active) & 15) return fail(GNN_ERR_INVALID_ARG, __fn, "dz_active must be 16-byte aligned");
+  }
   if (p->M < 0 || p->Nr < 1 || p->Nr > 128 || p->k1 < 1 || p->k2 < 0 || p->k1 + p->k2 > KMAX)
     return fail(GNN_ERR_UNSUPPORTED, __fn, "needs 1 <= Nr <= 128 and k1 + k2 <= 384");
   const bool planes_only = p->a_planes && !p->a1;
@@ -1083,17 +1110,37 @@ static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void
       // (ABI 25) the plain g form's block scale from the producer's row-group maxima (row blocks are
       // whole 32-row chunks, so every block covers whole GNN_ROWMAX_ROWS groups)
       a.growmax = (!a.dz && a.g) ? p->g_rowmax : nullptr;
+      if (dz_active && !(tn_h2_ok(a) && a.dz && !a.gout && !a.cptr))
+        return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active outside the half-pair dz-form TN's shapes");
       if (p->math != GNN_MATH_F32 && tn_h2_ok(a)) {
-        // a shard-sized M (the dz form): split-K block pairs over half as many row blocks (round 6)
+        // (ABI 28) the call-side CSC sum below also writes dz's activity flags (past the slabs) where
+        // they pay, and the TN walks them: the same kernel the caller's own flagged CSC sum reaches
+        const bool call_side = a.cptr && !tn_csc_in_kernel(tn_h2_rows_per_block(a.M, true));
+        uint8_t* ws_flags = nullptr;
+        if (call_side && tn_active_pays(a.M)) {
+          const size_t off = (size_t)nblk * stride * sizeof(float);
+          if (workspace_bytes < off + (size_t)tn_active_bytes(a.M) || (reinterpret_cast<uintptr_t>(workspace) & 15))
+            return fail(GNN_ERR_WORKSPACE, __fn, "workspace too small for the activity flags (gnn_gemm_tn_workspace_size)");
+          ws_flags = static_cast<uint8_t*>(workspace) + off;
+        }
+        a.dz_active = dz_active ? dz_active : ws_flags;
+        // a shard-sized M (the dz form): split-K block pairs over half as many row blocks (round 6).
+        // The flag-driven kernel never splits K, but it runs the row blocks of the dense call at the
+        // same M (nred of them, rows_per_block each), so its sums are the dense call's, bit for bit
         int nred = nblk;
-        const bool ks = a.dz && a.M <= tn_ksplit_max_m();
-        if (ks) {
+        const bool ksr = a.dz && a.M <= tn_ksplit_max_m();
+        const bool ks = ksr && !a.dz_active;
+        if (ksr) {
           const int64_t chunks = ceil_div(a.M, 32), per = ceil_div(chunks, 128);
           nred = (int)ceil_div(chunks, per);
           a.rows_per_block = per * 32;
         }
         if (a.rows_per_block != tn_h2_rows_per_block(a.M, a.dz != nullptr))
           return fail(GNN_ERR_HIP, __fn, "internal: TN row-block rule mismatch");
+        if (a.dz_active) {  // the block's chunk list is a fixed array
+          if (a.rows_per_block / GNN_ACTIVE_ROWS > TN_ACT_CAP)
+            return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active: row block beyond the chunk list's capacity");
+        }
         if (a.cptr && !tn_csc_in_kernel(a.rows_per_block)) {
           // (ABI 26) rows of more than one 64-row group per wave: the folded CSC sum would run two
           // dependent gather rounds per wave ahead of the chunk loop (full configs[1] graph, 800 rows a
@@ -1101,12 +1148,17 @@ static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void
           gnn_agg_params ag{};
           ag.mode = GNN_AGG_SUM;
           ag.transpose = 1;
-          const gnn_status s = gnn_aggregate_f32(p->dz_graph, &ag, p->dz_u, p->ldu, p->dz_cols,
-                                                 const_cast<float*>(p->dz), p->lddz, stream);
+          gnn_agg_active act{};
+          act.row_active = ws_flags;
+          act.active_with = p->dz + p->dz_cols;
+          act.ld_active_with = p->lddz;
+          act.active_with_cols = nproj - p->dz_cols;
+          const gnn_status s = gnn_aggregate_active_f32(p->dz_graph, &ag, p->dz_u, p->ldu, p->dz_cols,
+                                                        const_cast<float*>(p->dz), p->lddz, &act, stream);
           if (s != GNN_OK) return s;
           a.cptr = nullptr;
         }
-        launch_tn_h2(a, ks ? 2 * nred : nblk, st, ks);
+        launch_tn_h2(a, ks ? 2 * nred : nred, st, ks);
         GNN_LAUNCH_CHECK();
         slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nred, out, n_out, sqo);
         GNN_LAUNCH_CHECK();

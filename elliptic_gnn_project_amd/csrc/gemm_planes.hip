@@ -576,10 +576,23 @@ __device__ __forceinline__ float tn_csc_fold(const TNArgs& a, int64_t mbeg, int6
 // transposed mean of the output layer, Σ over each row's CSC slots of u[src] (u = dlogits / deg
 // from the CE launch) — with tn_csc_fold below, writes them to dz and reads them back as before:
 // the separate F = 2 CSC-sum launch of the step is gone.
-template <int KT, bool GOUT, int LAB = 0, int NW = 4, bool GF = false, int KS = 1, bool CSC = false>
+// ACT (ABI 28; the dz form, no gout, no fold, KS = 1): a.dz_active flags the 16-row chunks whose dz
+// rows can be nonzero (a train row or a neighbour of one: a fifth of the headline graph under the
+// rolling train window).  The prologue lists the flagged chunks of this block's OWN row block, in
+// ascending order, and the scale bound, the dz ring, the A / h prefetches and the row masks walk
+// that list instead of mbeg + 16c.  The row blocks and the order inside them are the dense
+// kernel's, and a skipped chunk would have added exact zeros, so every output is bit for bit the
+// dense kernel's: a block of an idle timestep writes its zero slab at once, and the blocks that hold
+// the train window stream A and h with the memory system to themselves.  (Dealing the flagged
+// chunks out over all blocks was built and measured, r117: TN 84.8 -> 33.5 us, but it regroups the
+// f32 sums, and Adam grows that 1e-7 difference to 1e-3 in the logits within 25 steps.)
+// Unflagged chunks are never read: a non-finite A or h row there no longer reaches dW (the dense
+// product's 0 · NaN).
+template <int KT, bool GOUT, int LAB = 0, int NW = 4, bool GF = false, int KS = 1, bool CSC = false, bool ACT = false>
 __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
   static_assert(KS == 1 || (KS == 2 && NW == 8), "split-K: the 8-wave form");
+  static_assert(!ACT || (NW == 8 && !GOUT && !GF && KS == 1 && !CSC && !(LAB & 16)), "ACT: the plain dz form");
   constexpr int T = 64 * NW;
   constexpr int NPA = (2 * PT_ROWS * (PT_MAXLD / 8) + T - 1) / T;  // A pieces per thread per chunk (6 / 3)
   constexpr int RP = PT_ROWS / (T / 128);                           // G rows per thread per chunk (8 / 4)
@@ -589,6 +602,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   __shared__ __attribute__((aligned(16))) uint16_t At[2][2 * PT_APL];
   __shared__ float dzL[2][256];
   __shared__ float redm[2 * NW];
+  __shared__ int32_t clist[ACT ? TN_ACT_CAP : 1];  // ACT: this block's chunk ids (fixed size, not M's)
+  __shared__ int32_t actw[NW];                     // ACT: the waves' flag counts
   constexpr int NU = 2 * NPA + RP / 2 + 2 * RP + RP / 2 + 3;  // staging units per chunk
   constexpr int NG = 3 * KTW;                                 // MFMA gaps per chunk
   // A's register ring: RING sets of the NPA pieces, a chunk's loads issued RING chunks before
@@ -609,7 +624,31 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   const int pr = min(4 * ktb, (ld - 32 * kt0) >> 3);        // 16-byte A pieces per row
   const int64_t mbeg = (int64_t)rblk * a.rows_per_block;
   const int64_t mend = min(a.M, mbeg + a.rows_per_block);
-  const int nch = mend > mbeg ? (int)((mend - mbeg + PT_ROWS - 1) / PT_ROWS) : 0;
+  const int Mi = (int)a.M;
+  int nch = mend > mbeg ? (int)((mend - mbeg + PT_ROWS - 1) / PT_ROWS) : 0;
+  if constexpr (ACT) {
+    // this block's row block, chunk by chunk: thread t reads the flag of chunk q0 + t (a row block
+    // holds at most TN_ACT_CAP <= T chunks), the flagged ones are numbered by a ballot per wave and
+    // the waves' counts in order, and their ids go to clist in ascending order
+    const int nf = (Mi + PT_ROWS - 1) / PT_ROWS;
+    const int q0 = (int)(mbeg / PT_ROWS), q1 = min(nf, (int)((mbeg + a.rows_per_block) / PT_ROWS));
+    const int q = q0 + tid;
+    const bool on = q < q1 && a.dz_active[q] != 0;
+    const uint64_t bm = __ballot(on);
+    if (lane == 0) actw[wave] = __popcll(bm);
+    __syncthreads();
+    int wbase = 0, n_act = 0;
+#pragma unroll
+    for (int w2 = 0; w2 < NW; ++w2) {
+      const int v = actw[w2];
+      wbase += w2 < wave ? v : 0;
+      n_act += v;
+    }
+    const int pos = wbase + __popcll(bm & ((1ull << lane) - 1ull));
+    if (on && pos < TN_ACT_CAP) clist[pos] = q;
+    __syncthreads();
+    nch = min(n_act, TN_ACT_CAP);
+  }
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   const int wrow = 32 * (wave & 3);                             // this wave's dW rows
   const int tbase = NW == 4 ? 0 : (wave >> 2) * KTW;            // and k-tiles [tbase, tbase + ntl) of the block
@@ -684,7 +723,26 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
         }
       }
     }
-    for (int64_t r0 = mbeg + tid; !GF && !CSC && r0 < mend; r0 += 4 * T) {
+    if constexpr (ACT) {  // the listed chunks' rows: 16 threads a chunk, 4 chunks per thread per pass
+      constexpr int CP = T / PT_ROWS;
+      for (int k0 = tid / PT_ROWS; k0 < nch; k0 += 4 * CP) {
+        float v[4][MAXPROJ];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int64_t r = min(clist[min(k0 + CP * u, nch - 1)] * PT_ROWS + (tid & (PT_ROWS - 1)), Mi - 1);
+#pragma unroll
+          for (int q = 0; q < MAXPROJ; ++q) v[u][q] = a.dz[r * a.lddz + min(q, nq - 1)];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          float s = 0.f;
+#pragma unroll
+          for (int q = 0; q < MAXPROJ; ++q) s += q < nq ? fabsf(v[u][q]) : 0.f;
+          zm = fmaxf(zm, k0 + CP * u < nch ? s : 0.f);
+        }
+      }
+    }
+    for (int64_t r0 = mbeg + tid; !GF && !CSC && !ACT && r0 < mend; r0 += 4 * T) {
       float v[4][MAXPROJ];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -727,31 +785,61 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     gunsc = ldexpf(1.0f, E - 4 - 11 - a.ap_exp);             // slab = acc · 2^-11 / gsc / 2^ap_exp
   };
 
-  const int Mi = (int)a.M;
-  auto ldbase = [&](int c) __attribute__((always_inline)) { return min((int)mbeg + c * PT_ROWS, Mi - PT_ROWS); };
   const int clast = max(nch - 1, 0);
+  // ACT: the id of the block's chunk c (wave-uniform; c <= clast)
+  auto cid = [&](int c) __attribute__((always_inline)) { return __builtin_amdgcn_readfirstlane(clist[c]); };
+  auto ldbase = [&](int c) __attribute__((always_inline)) {
+    if constexpr (ACT) return min(cid(c) * PT_ROWS, Mi - PT_ROWS);
+    else return min((int)mbeg + c * PT_ROWS, Mi - PT_ROWS);
+  };
+  // the rows [lo, hi) of the 16 loaded at ldbase(k) that are chunk k's own (a tail chunk's base is
+  // shifted back; past the block's last chunk: none)
+  auto zrange = [&](int k, int& lo, int& hi) __attribute__((always_inline)) {
+    if constexpr (ACT) {
+      const int q = cid(min(k, clast)), mb = min(q * PT_ROWS, Mi - PT_ROWS);
+      lo = k < nch ? q * PT_ROWS - mb : PT_ROWS;
+      hi = min(Mi, (q + 1) * PT_ROWS) - mb;
+    } else {
+      const int mb = ldbase(k);
+      lo = (int)mbeg + k * PT_ROWS - mb;
+      hi = (int)mend - mb;
+    }
+  };
+  // ACT: base rows of the block's chunks min(c + 2, clast) / min(c + 3, clast) and chunk c + 2's own
+  // rows, read from the list once at the top of chunk c (the staging units then hold no LDS read)
+  // glo: the first own row of the chunk whose G rows are being formed — a shifted-back tail chunk
+  // re-loads rows of the chunk before it, which may be unflagged: their h must not reach dzᵀ·h
+  int ab2 = 0, ab3 = 0, az2lo = 0, az2hi = 0, glo = 0;
   u32x4 ra[RING][NPA];
   float rg[RGN][RP];
   float rz = 0.f;
-  auto load_a = [&](int s, int j, int c) __attribute__((always_inline)) {
-    ra[s][j] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)goff[j], ldbase(c) * ld * 2, 0);
+  auto load_a_at = [&](int s, int j, int mb) __attribute__((always_inline)) {
+    ra[s][j] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)goff[j], mb * ld * 2, 0);
   };
-  auto load_g = [&](int sg, int c) __attribute__((always_inline)) {
-    uint32_t o = (uint32_t)((ldbase(c) + RP * go) * hld);
+  auto load_a = [&](int s, int j, int c) __attribute__((always_inline)) { load_a_at(s, j, ldbase(c)); };
+  auto load_g_at = [&](int sg, int mb) __attribute__((always_inline)) {
+    uint32_t o = (uint32_t)((mb + RP * go) * hld);
 #pragma unroll
     for (int i = 0; i < RP; ++i) {
       rg[sg][i] = hb[o];
       o += (uint32_t)hld;
     }
   };
-  auto load_z = [&](int c) __attribute__((always_inline)) {
-    if constexpr (!GF) rz = a.dz[(uint32_t)((ldbase(c) + zr) * (int)a.lddz + zqc)];
+  auto load_g = [&](int sg, int c) __attribute__((always_inline)) { load_g_at(sg, ldbase(c)); };
+  auto load_z_at = [&](int mb) __attribute__((always_inline)) {
+    if constexpr (!GF) rz = a.dz[(uint32_t)((mb + zr) * (int)a.lddz + zqc)];
+  };
+  auto load_z = [&](int c) __attribute__((always_inline)) { load_z_at(ldbase(c)); };
+  auto put_zlh = [&](int k, int lo, int hi, float v) __attribute__((always_inline)) {
+    if constexpr (GF) return;
+    const bool ok = tid < PT_ROWS * MAXPROJ && zq < a.nproj && zr >= lo && zr < hi;
+    if (T == 256 || tid < 256) dzL[k & 1][tid] = ok ? v : 0.0f;
   };
   auto put_zv = [&](int k, float v) __attribute__((always_inline)) {
     if constexpr (GF) return;
-    const int mb = ldbase(k);
-    const bool ok = tid < PT_ROWS * MAXPROJ && zq < a.nproj && zr >= (int)mbeg + k * PT_ROWS - mb && zr < (int)mend - mb;
-    if (T == 256 || tid < 256) dzL[k & 1][tid] = ok ? v : 0.0f;
+    int lo, hi;
+    zrange(k, lo, hi);
+    put_zlh(k, lo, hi, v);
   };
   auto put_z = [&](int k) __attribute__((always_inline)) { put_zv(k, rz); };
 
@@ -785,6 +873,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
       e[i] = g * gsc;  // exact (a power of two)
       return;
     }
+    if constexpr (ACT) rg[sg][i] = RP * go + i >= glo ? rg[sg][i] : 0.0f;  // (both halves: idempotent)
     if (half == 0) {
       const float4 z = zv[i];
       float g = z.x * pcol[0];
@@ -830,8 +919,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     const int sa = RING == 1 ? 0 : (par ^ 1);
     const int sg = RGN == 1 ? 0 : (par ^ 1);  // chunk c + 1's G rows
     if (k < Z0) {
-      if (k & 1) load_a(sa, k >> 1, min(c + 1 + RING, clast));
-      else put_a(sa, k >> 1, c + 1);
+      if (k & 1) {
+        if constexpr (ACT) load_a_at(sa, k >> 1, ab2);  // (RING = 1: chunk min(c + 2, clast))
+        else load_a(sa, k >> 1, min(c + 1 + RING, clast));
+      } else {
+        put_a(sa, k >> 1, c + 1);
+      }
     } else if (k < G0) {
       z_read(c + 1, 2 * (k - Z0), 2);
     } else if (k < S0) {
@@ -841,10 +934,16 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     } else if (k == P0) {
       g_put(c + 1);
     } else if (k == P0 + 1) {
-      load_g(sg, min(c + 1 + RGN, clast));
+      if constexpr (ACT) load_g_at(sg, ab2);  // (RGN = 1: chunk min(c + 2, clast))
+      else load_g(sg, min(c + 1 + RGN, clast));
     } else if (k == P0 + 2) {
-      put_z(c + 2);
-      load_z(min(c + 3, clast));
+      if constexpr (ACT) {
+        put_zlh(c + 2, az2lo, az2hi, rz);
+        load_z_at(ab3);
+      } else {
+        put_z(c + 2);
+        load_z(min(c + 3, clast));
+      }
     }
   };
 
@@ -859,6 +958,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   auto compute = [&](int c, auto parc) __attribute__((always_inline)) {
     constexpr int par = decltype(parc)::value;
     const int buf = c & 1;
+    if constexpr (ACT) {  // the list entries this chunk's staging units need, beside the fragment reads
+      glo = az2lo;  // (chunk c + 1's, whose G rows this chunk's units form)
+      zrange(c + 2, az2lo, az2hi);
+      ab2 = ldbase(min(c + 2, clast));
+      ab3 = ldbase(min(c + 3, clast));
+    }
     f16x8 gf[3], af[2][2];  // G: hi', hi, lo; A: hi, lo
 #pragma unroll
     for (int p = 0; p < 3; ++p) gf[p] = *reinterpret_cast<const f16x8*>(Gt[buf] + p * PT_GPL + gfo);
@@ -934,6 +1039,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
 #pragma unroll
     for (int j = 0; j < NPA; ++j) put_a(0, j, 0);
     z_read(0, 0, RP);
+    if constexpr (ACT) {
+      zrange(0, glo, az2hi);
+      zrange(1, az2lo, az2hi);  // (the first chunk of the loop shifts it into glo)
+    }
 #pragma unroll
     for (int i = 0; i < RP; ++i) {
       g_row(i, 0, 0, 0);
@@ -1367,6 +1476,10 @@ void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks) {
   if (!a.dz) {  // the g form
     if (a.ap_ld == 176) gemm_tn_h2_kernel<6, false, 0, 8, true><<<nblk, 512, 0, st>>>(a);
     else gemm_tn_h2_kernel<11, false, 0, 8, true><<<nblk, 512, 0, st>>>(a);
+    return;
+  }
+  if (a.dz_active) {  // (ABI 28) the flagged chunks only (the caller checked: no gout, no fold, not ks)
+    gemm_tn_h2_kernel<11, false, 0, 8, false, 1, false, true><<<nblk, 512, 0, st>>>(a);
     return;
   }
   if (a.cptr) {  // (ABI 26) the CSC sum of u folded in (tn_h2_ok: no gout)

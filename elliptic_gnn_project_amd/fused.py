@@ -63,6 +63,12 @@ _SIDE_PREP = os.environ.get("GNNMP_SIDE_PREP", "0") == "1"
 # u) itself, block by block (gnn_gemm_tn_params.dz_graph, ABI 26, bit for bit), instead of a separate
 # F = 2 CSC-sum launch before it; GNNMP_TN_CSC=0 keeps the separate launch (A/B)
 _TN_CSC = os.environ.get("GNNMP_TN_CSC", "1") != "0"
+# The same backward at full-graph size: the CSC-sum launch that finishes dz also flags the 16-row
+# chunks of dz that hold a nonzero (a train row or a neighbour of one: a fifth of the chunks under the
+# rolling train window), and each row block of the layer-1 TN walks only those of its rows
+# (gnn_gemm_tn_active_f32, ABI 28; the same bits) — where gnn_gemm_tn_active_pays(N), a rule of N
+# alone; GNNMP_TN_ACTIVE=0 runs the dense TN (A/B)
+_TN_ACTIVE = os.environ.get("GNNMP_TN_ACTIVE", "1") != "0"
 # GCN backward: the skinny masked-gradient NT also writes its column sums (the layer below's bias
 # gradient, gnn_gemm_nt_params.colsum_part) instead of a separate colsum pass; GNNMP_NT_COLSUM=0: A/B
 _NT_COLSUM = os.environ.get("GNNMP_NT_COLSUM", "1") != "0"
@@ -230,7 +236,7 @@ def gemm_nt(a1, bt, n, a2=None, bias=None, relu=False, dropout_p=0.0, seed=0, pr
 
 
 def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gout=None, math=None,
-            planes=None, check_planes=False, sq=None, sq_skip=(0, 0), row_exp=None, csc=None):
+            planes=None, check_planes=False, sq=None, sq_skip=(0, 0), row_exp=None, csc=None, dz_active=None):
     """((Gᵀ·a1, Gᵀ·a2), db, dzᵀ·h, dzsum) from one flat fp32 buffer — the MFMA TN kernel.
     ``planes``: A read from a split image (a1 / a2 may be None); ``check_planes`` as gemm_nt.
     ``sq`` = (partials buffer, step tensor) of train_ops.grad_sq_request: the reduce also writes
@@ -239,7 +245,9 @@ def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gou
     ``row_exp``: the int32 row exponents a half-pair NT wrote for [a1 | a2]; with math="half_pair"
     and the plain g form the TN then runs in half-pair arithmetic (gnn_gemm_tn_params.row_exp).
     ``csc`` = (plan, u): the half-pair dz-form TN forms dz[:, :u.size(1)] itself as the transposed
-    SUM of u over the plan (gnn_gemm_tn_params.dz_graph, ABI 26) instead of reading it."""
+    SUM of u over the plan (gnn_gemm_tn_params.dz_graph, ABI 26) instead of reading it.
+    ``dz_active``: uint8 flags, one per 16 rows of dz, 0 = the group's dz rows are all zero; the
+    half-pair dz-form TN then walks only the flagged chunks (gnn_gemm_tn_active_f32, ABI 28)."""
     if planes is not None:
         M, k1, k2, dev = planes.n, planes.k1, planes.k2, planes.img.device
     else:
@@ -286,7 +294,13 @@ def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gou
         e0 = torch.cuda.Event(enable_timing=True)
         e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-    _lib.call("gnn_gemm_tn_f32", p, out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _lib.stream_handle(dev))
+    if dz_active is not None:
+        if dz_active.dtype != torch.uint8 or dz_active.numel() < (M + _lib.ACTIVE_ROWS - 1) // _lib.ACTIVE_ROWS:
+            raise ValueError("dz_active: uint8, one per 16 rows of dz")
+        _lib.call("gnn_gemm_tn_active_f32", p, dz_active.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+                  _lib.stream_handle(dev))
+    else:
+        _lib.call("gnn_gemm_tn_f32", p, out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _lib.stream_handle(dev))
     if sq is not None:
         from .train_ops import grad_sq_produced
 
@@ -354,6 +368,26 @@ def _csc_fold(ctx, dz, u, hscale):
                    csc=csc):
         return None
     return csc
+
+
+def _tn_active_flags(ctx, dz, hscale):
+    """An empty uint8 flag buffer (one per 16 rows of dz) when the 2-layer SAGE backward's one TN
+    (layer 1, half-pair image, dz form, no input gradient) walks activity flags at this size
+    (gnn_gemm_tn_active_pays: a rule of the row count alone), else None (the dense TN)."""
+    L = ctx.meta[0]
+    N = dz.size(0)
+    if not _TN_ACTIVE or L != 2 or ctx.needs_input_grad[0] or ctx.bimgs[0] is not None:
+        return None
+    saved = ctx.saved_tensors
+    if saved[L] is not None or getattr(ctx, "image", None) is None or not isinstance(ctx.image[0], HalfPairImage):
+        return None  # layer 1 not on the half-pair image of [agg | x]
+    if not _lib.load().gnn_gemm_tn_active_pays(N):
+        return None
+    hs1, Wl0 = saved[1], saved[2 * L - 1]
+    if not gemm_tn(Wl0.size(0), None, None, h=hs1, hscale=hscale, planes=ctx.image[0], check_planes=True, dz=dz,
+                   proj=ctx.P):
+        return None
+    return torch.empty((N + _lib.ACTIVE_ROWS - 1) // _lib.ACTIVE_ROWS, dtype=torch.uint8, device=dz.device)
 
 
 def gemm_tn_input(nr: int, x: torch.Tensor, g: torch.Tensor):
@@ -538,6 +572,7 @@ class _FusedSAGE(torch.autograd.Function):
         hscale = 1.0 / (1.0 - p) if p > 0 else 1.0
         N = dlogits.size(0)
         csc_fold = None  # (plan, u) when the layer's TN forms dz's meanᵀ half itself (ABI 26)
+        act = None       # dz's 16-row activity flags, written by the CSC sum, when the TN walks them (ABI 28)
         buf = getattr(dlogits, "_gnnmp_dz", None)  # the fused CE's [N, 2C] buffer, dlogits its right half
         if (buf is not None and buf.shape == (N, 2 * C) and dlogits.stride() == (2 * C, 1)
                 and dlogits.data_ptr() == buf.data_ptr() + C * buf.element_size()):
@@ -546,7 +581,11 @@ class _FusedSAGE(torch.autograd.Function):
             if u is not None:  # meanᵀ as a plain CSC sum: MEAN_BWD's per-slot terms precomputed, same bits
                 csc_fold = _csc_fold(ctx, dz, u, hscale)
                 if csc_fold is None:
-                    aggregate(plan, u, _lib.AGG_SUM, transpose=True, out=dz[:, :C])
+                    act = _tn_active_flags(ctx, dz, hscale)
+                    if act is not None:
+                        aggregate(plan, u, _lib.AGG_SUM, transpose=True, out=dz[:, :C], active=(act, dz[:, C:]))
+                    else:
+                        aggregate(plan, u, _lib.AGG_SUM, transpose=True, out=dz[:, :C])
             else:
                 aggregate(plan, dlogits, _lib.AGG_MEAN_BWD, transpose=True, nodew=plan.deg, out=dz[:, :C])
         else:
@@ -597,7 +636,8 @@ class _FusedSAGE(torch.autograd.Function):
                     a_l, im = aggregate(plan, hs[0], _lib.AGG_MEAN, nodew=plan.deg), None
             if l == L - 2:
                 dW, db, dW2, dzs = gemm_tn(fo, a_l, hs[l], dz=dz, proj=P, h=hs[l + 1], hscale=hscale,
-                                           gout=gout, planes=im, sq=sq, sq_skip=(-2 * C, -C), csc=csc_fold)
+                                           gout=gout, planes=im, sq=sq, sq_skip=(-2 * C, -C), csc=csc_fold,
+                                           dz_active=act if (im is not None and gout is None) else None)
                 grads[3 * (L - 1) + 0] = dW2[:C]
                 grads[3 * (L - 1) + 1] = dzs[C:]
                 grads[3 * (L - 1) + 2] = dW2[C:]

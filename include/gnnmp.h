@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 27
+#define GNNMP_ABI_VERSION 28
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -172,6 +172,31 @@ typedef struct {
 /* Generic fp32 aggregation: y[r, 0:F] for r in [0, N). */
 gnn_status gnn_aggregate_f32(const gnn_graph* g, const gnn_agg_params* p, const float* x,
                              int64_t ldx, int64_t F, float* y, int64_t ldy, gnn_stream_t stream);
+
+/* Row-group granularity of the activity flags (ABI 28). */
+#define GNN_ACTIVE_ROWS 16
+
+/* (ABI 28) Activity flags of an aggregation's output, written by the launch that finishes it: one
+ * byte per group of GNN_ACTIVE_ROWS rows, row_active[r / 16] != 0 iff some row of the group has a
+ * nonzero value (v != 0.0f, so NaN counts) among its F outputs or among active_with[r, 0:cols] —
+ * the other columns of the buffer y is a slice of (the SAGE backward's dz = [Σ_CSC u | dlogits]:
+ * y the left half, active_with the right).  A superset is legal, a 0 on a nonzero group never: a
+ * group holding a row that a later pass of the call finishes is flagged 1.  The weight-gradient TN
+ * reads them as its dz_active (gnn_gemm_tn_active_f32).  row_active: [ceil(N / 16)] bytes, 4-byte
+ * aligned; active_with optional (cols 0..4, ld_active_with >= cols). */
+typedef struct {
+  uint8_t* row_active;
+  const float* active_with;
+  int64_t ld_active_with;
+  int32_t active_with_cols;
+} gnn_agg_active;
+
+/* gnn_aggregate_f32 that also writes `act` (NULL or act->row_active NULL: exactly gnn_aggregate_f32).
+ * Only the narrow slot-parallel form takes it (F <= 4; F <= 2 for GCN; not EDGE_W): every other
+ * form is refused with GNN_ERR_UNSUPPORTED before any launch. */
+gnn_status gnn_aggregate_active_f32(const gnn_graph* g, const gnn_agg_params* p, const float* x, int64_t ldx,
+                                    int64_t F, float* y, int64_t ldy, const gnn_agg_active* act,
+                                    gnn_stream_t stream);
 
 /* bf16-storage form: x and y hold bf16 ([rows, F], ld in elements), f32 accumulation in plan
  * order, y rounded once (RNE).  Modes SUM / MEAN / MEAN_BWD / GCN (no EDGE_W); addend f32. */
@@ -552,6 +577,25 @@ typedef struct {
 gnn_status gnn_gemm_tn_workspace_size(int64_t M, int64_t Nr, int64_t Kc, int32_t nproj, size_t* bytes);
 gnn_status gnn_gemm_tn_f32(const gnn_gemm_tn_params* p, float* out, void* workspace, size_t workspace_bytes,
                            gnn_stream_t stream);
+/* (ABI 28) gnn_gemm_tn_f32 over the row chunks whose dz can be nonzero.  dz_active: [ceil(M / 16)]
+ * bytes, 16-byte aligned, one per GNN_ACTIVE_ROWS rows of dz; a 0 promises that every dz value of
+ * the group is zero (gnn_aggregate_active_f32 writes such flags).  The half-pair dz form with h, no
+ * gout and no dz_graph only, at every M >= 16 (never split-K): each row block of the dense call
+ * walks only its flagged chunks, in order, so on a graph whose train rows sit in a few timesteps
+ * most blocks finish at once and the rest stream A and h uncontended.  A skipped chunk would have
+ * added exact zeros: the output is bit-identical to gnn_gemm_tn_f32 on the same operands, whatever
+ * the flags, as long as they keep their promise.  Unflagged chunks of A and h are never read: a
+ * non-finite value there no longer reaches the output (the dense product's 0 · NaN does).  Every
+ * other form is refused with GNN_ERR_UNSUPPORTED before any launch.  dz_active NULL: exactly
+ * gnn_gemm_tn_f32.
+ * A gnn_gemm_tn_f32 call with dz_graph that launches the CSC sum itself (row blocks too large for
+ * its kernel) takes the same route on its own when gnn_gemm_tn_active_pays(M), with flags kept
+ * past the slabs of the workspace (gnn_gemm_tn_workspace_size counts them). */
+gnn_status gnn_gemm_tn_active_f32(const gnn_gemm_tn_params* p, const uint8_t* dz_active, float* out,
+                                  void* workspace, size_t workspace_bytes, gnn_stream_t stream);
+/* 1 when the flags pay at M rows: the dz-form row block is larger than the in-kernel CSC fold takes
+ * (more than 448 rows a block, M > 114,688) — a rule of M alone, so every route to the TN agrees. */
+int gnn_gemm_tn_active_pays(int64_t M);
 /* The number nb of norm partials a call with sq_partial writes for an out of n_out floats (ABI 20). */
 gnn_status gnn_gemm_tn_sq_blocks(int64_t n_out, int32_t* nb);
 /* 1 when the call would read A from p->a_planes (the f32 A operands are then not needed), else 0.
