@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -153,6 +153,9 @@ class GnnGemmTNParams(ctypes.Structure):
     ]
 
 
+RANK_TILE = 1024  # GNN_RANK_TILE (ABI 29)
+RANK_BOOT_LDS_MAX_N = 32768  # GNN_RANK_BOOT_LDS_MAX_N
+RANK_STATUS_NAN, RANK_STATUS_SEGMENT, RANK_STATUS_INDEX = 1, 2, 4
 ROWMAX_ROWS = 16  # GNN_ROWMAX_ROWS (ABI 25)
 ACTIVE_ROWS = 16  # GNN_ACTIVE_ROWS (ABI 28)
 
@@ -405,6 +408,22 @@ SIGNATURES = {
     "gnn_time_inject_sin_f32": (
         ctypes.c_int,
         [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr],
+    ),
+    "gnn_rank_plan_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_rank_plan_build": (
+        ctypes.c_int,
+        [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr],
+    ),
+    "gnn_rank_ap_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_rank_ap": (
+        ctypes.c_int,
+        [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr],
+    ),
+    "gnn_rank_bootstrap_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_rank_bootstrap": (
+        ctypes.c_int,
+        [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+         c_ptr, c_ptr, c_size, c_ptr],
     ),
 }
 

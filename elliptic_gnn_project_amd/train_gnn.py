@@ -11,7 +11,10 @@ Kept from the reference (same names, same YAML keys, same semantics):
                                   PR-AUC, best-state restore, temperature scaling, metrics.json,
                                   best.ckpt, optional hub ablation)
 New optional keys: ``synthetic`` (dict of synthetic_elliptic kwargs, used when no
-processed graph exists), ``graph_file`` (PyG-free .npz written by dataset_elliptic.save_graph).
+processed graph exists), ``graph_file`` (PyG-free .npz written by dataset_elliptic.save_graph),
+``device_metrics`` (default false: validation PR-AUC per epoch and the per-timestep test PR-AUC on the
+device, rank_metrics / libgnnmp K14; full-batch on a CUDA device only — the mini-batch path keeps the
+host metrics).
 The mini-batch path (:212-245, :260-276, :329-348) runs on loader.NeighborLoader (K11 sampling).
 """
 from __future__ import annotations
@@ -430,6 +433,20 @@ def eval_split(model, data, edge_index, mask, dist=None, num_nodes=None):
     return y[m], probs[m], logits
 
 
+@torch.no_grad()
+def eval_split_device(model, data, edge_index, dist=None, num_nodes=None):
+    """eval_split without the host copies (``device_metrics``): (labels [N], illicit probabilities [N],
+    logits) of ALL nodes in the global node order, on the device; the caller masks on the device."""
+    model.eval()
+    logits = model(data.x, edge_index, data.timestep if _model_uses_time_embed(model) else None)
+    if dist is not None:
+        logits = gather_rows(logits.float(), data.nodes, num_nodes, dist)
+        y = gather_rows(data.y, data.nodes, num_nodes, dist)
+    else:
+        y = data.y
+    return y, torch.softmax(logits, dim=1)[:, 1].detach(), logits
+
+
 class RunLogger:
     """``training_log.csv`` (epoch, train_loss, val_pr_auc) as src/utils/logger.py:5-27 writes it,
     plus the TensorBoard scalars when tensorboard is importable (it is optional here)."""
@@ -554,6 +571,10 @@ def per_timestep_pr_auc(y_te: np.ndarray, p_te: np.ndarray, test_ts: np.ndarray)
     for t in sorted(set(int(v) for v in test_ts.tolist())):
         idx = test_ts == t
         pr_by_t.append(float("nan") if idx.sum() == 0 else pr_auc_illicit((y_te[idx] == 1).astype(int), p_te[idx]))
+    return _by_time_summary(out, pr_by_t)
+
+
+def _by_time_summary(out: Dict, pr_by_t) -> Dict:
     out["test_pr_auc_by_time"] = pr_by_t
     if pr_by_t:
         out["pr_auc_last1"] = float(pr_by_t[-1])
@@ -562,6 +583,18 @@ def per_timestep_pr_auc(y_te: np.ndarray, p_te: np.ndarray, test_ts: np.ndarray)
         if len(pr_by_t) >= 5:
             out["pr_auc_last5"] = float(sum(pr_by_t[-5:]) / 5)
     return out
+
+
+def per_timestep_pr_auc_device(y: torch.Tensor, probs: torch.Tensor, timestep: torch.Tensor,
+                               test_mask: torch.Tensor) -> Dict:
+    """per_timestep_pr_auc from ONE segmented average-precision call over the test mask (device tensors
+    over all nodes); a timestep without an illicit node gets 0.0, as the host path's sklearn returns."""
+    from . import rank_metrics
+
+    _, ap, _ = rank_metrics.average_precision_by_group(probs, y, timestep, mask=test_mask)
+    if ap.numel() == 0:
+        return {}
+    return _by_time_summary({}, [float(v) for v in ap.cpu().tolist()])
 
 
 def hub_edge_mask(edge_index: torch.Tensor, num_nodes: int, frac: float):
@@ -578,7 +611,13 @@ def hub_edge_mask(edge_index: torch.Tensor, num_nodes: int, frac: float):
 
 
 def main(cfg: Dict) -> Dict:
-    """src/train_gnn.py:282-564 on libgnnmp, single GPU or timestep-partitioned over ranks."""
+    """src/train_gnn.py:282-564 on libgnnmp, single GPU or timestep-partitioned over ranks.
+
+    New optional key ``device_metrics`` (default false): on a CUDA device, full-batch, the per-epoch
+    validation PR-AUC and the final ``test_pr_auc_by_time`` / ``pr_auc_last{1,3,5}`` are computed on the
+    device (rank_metrics, libgnnmp K14) — one scalar crosses to the host per epoch and the best state is
+    kept as device clones.  Under ``world_size`` > 1 every rank computes the same value from the gathered
+    logits (no new collective).  The mini-batch path keeps the host metrics whatever the key says."""
     dist, world, rank = _init_distributed(cfg)
     set_seed(cfg.get("seed", 42))  # same seed on every rank: identical initial weights
     is_main = rank == 0
@@ -625,6 +664,12 @@ def main(cfg: Dict) -> Dict:
         val_loader = NeighborLoader(data, num_neighbors=fanout, batch_size=bsz,
                                     input_nodes=data.val_mask.nonzero().view(-1), shuffle=False)
 
+    device_metrics = bool(cfg.get("device_metrics", False)) and device.type == "cuda" and not use_mini_batch
+    if device_metrics:
+        from . import rank_metrics
+
+        vm_dev = gmask("val_mask").to(device)
+
     best_val, best_state, bad = -1.0, None, 0
     patience = cfg.get("patience", 20)
     for epoch in range(1, cfg["max_epochs"] + 1):
@@ -634,13 +679,25 @@ def main(cfg: Dict) -> Dict:
         else:
             loss = train_epoch(model, data, ei, opt, loss_fn, scaler, use_amp, cfg, device, denom=n_train,
                                bucket=bucket, dist=dist)
-            y_val, p_val, _ = eval_split(model, data, ei, gmask("val_mask"), **ev)
-        pr_val = 0.0 if y_val.size == 0 else pr_auc_illicit((y_val == 1).astype(int), p_val)
+            if not device_metrics:
+                y_val, p_val, _ = eval_split(model, data, ei, gmask("val_mask"), **ev)
+        if device_metrics:  # AP over the validation mask on the device; one transfer: [AP, status word]
+            y_all, p_all, _ = eval_split_device(model, data, ei, **ev)
+            ap_dev, st_dev = rank_metrics.average_precision(p_all, y_all, vm_dev, check=False, return_status=True)
+            ap_st = torch.cat([ap_dev.view(1), st_dev.to(torch.float64)]).cpu()
+            if int(ap_st[1]) != 0:
+                rank_metrics.check_status(st_dev)
+            pr_val = float(ap_st[0])
+        else:
+            pr_val = 0.0 if y_val.size == 0 else pr_auc_illicit((y_val == 1).astype(int), p_val)
         if logger is not None:
             logger.log_epoch(epoch, loss, pr_val)
         if pr_val > best_val:
             best_val, bad = pr_val, 0
-            best_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
+            if device_metrics:
+                best_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+            else:
+                best_state = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
         else:
             bad += 1
         if is_main and (epoch % 10 == 0 or epoch == 1):
@@ -650,6 +707,8 @@ def main(cfg: Dict) -> Dict:
                 print("Early stopping.")
             break
     if best_state is not None:
+        if device_metrics:  # the device clones cross to the host once, here
+            best_state = {k: v.cpu() for k, v in best_state.items()}
         model.load_state_dict({k: v.to(device) for k, v in best_state.items()})
 
     T = None
@@ -672,7 +731,7 @@ def main(cfg: Dict) -> Dict:
         if dist is not None:
             dist.broadcast(T, 0)  # one temperature for every rank
 
-    def get_probs(edge_index_eval):
+    def get_probs_device(edge_index_eval):
         model.eval()
         with torch.no_grad():
             lg = model(data.x, edge_index_eval, data.timestep if _model_uses_time_embed(model) else None)
@@ -680,9 +739,13 @@ def main(cfg: Dict) -> Dict:
                 lg = gather_rows(lg.float(), data.nodes, N, dist)
             if T is not None:
                 lg = lg / T
-            return torch.softmax(lg, dim=1)[:, 1].cpu().numpy()
+            return torch.softmax(lg, dim=1)[:, 1]
 
-    probs = get_probs(ei)
+    def get_probs(edge_index_eval):
+        return get_probs_device(edge_index_eval).cpu().numpy()
+
+    probs_dev = get_probs_device(ei)
+    probs = probs_dev.cpu().numpy()
     y_np = full.y.numpy() if dist is not None else data.y.cpu().numpy()
     vm, tm = gmask("val_mask").cpu().numpy(), gmask("test_mask").cpu().numpy()
     ts = full.timestep.numpy() if dist is not None else data.timestep.cpu().numpy()
@@ -692,7 +755,12 @@ def main(cfg: Dict) -> Dict:
         else _max_f1_threshold(y_te, p_te)
     metrics = _metrics(y_te, p_te, thr, cfg) if y_te.size else {}
     metrics["best_val_pr_auc"] = best_val
-    metrics.update(per_timestep_pr_auc(y_np[tm], p_te, ts[tm]))
+    if device_metrics:
+        y_all = gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y
+        ts_dev = full.timestep.to(device) if dist is not None else data.timestep
+        metrics.update(per_timestep_pr_auc_device(y_all, probs_dev, ts_dev, gmask("test_mask").to(device)))
+    else:
+        metrics.update(per_timestep_pr_auc(y_np[tm], p_te, ts[tm]))
 
     frac = float(cfg.get("ablate_hubs_frac", 0.0))
     metrics_hub = None

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 28
+#define GNNMP_ABI_VERSION 29
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -824,6 +824,62 @@ gnn_status gnn_neighbor_sample(const gnn_graph* g, const int32_t* csr_eid, const
                                int32_t* n_id, int64_t node_cap, int32_t* e_src, int32_t* e_dst,
                                int32_t* e_id, int64_t edge_cap, int64_t* hop_nodes, int64_t* hop_edges,
                                void* workspace, size_t workspace_bytes, gnn_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K14 ranking metrics (ABI 29): sklearn.metrics.average_precision_score as src/utils/metrics.py:10-12
+ *     calls it, the per-timestep loop of src/train_gnn.py:497-519, precision_at_k
+ *     (metrics.py:37-39) and the replicates of src/analysis/bootstrap_compare.py          */
+/* ------------------------------------------------------------------------ */
+#define GNN_RANK_TILE 1024               /* order positions per block of the AP scan */
+#define GNN_RANK_BOOT_LDS_MAX_N 32768    /* bootstrap: n up to this histograms in LDS, above in global memory */
+/* bits of the device status word (OR-ed in by the calls; the caller zeroes and reads it) */
+#define GNN_RANK_STATUS_NAN 1            /* an included score is NaN */
+#define GNN_RANK_STATUS_SEGMENT 2        /* an included element's segment is outside [0, S): it was excluded */
+#define GNN_RANK_STATUS_INDEX 4          /* a bootstrap sample index is outside [0, n), or a plan is not whole */
+
+/*
+ * Rank plan of scores[n] (f32): order[n] holds the included elements (include[i] != 0; NULL = all)
+ * sorted by (segment ascending, score descending, index ascending) — segment[i] in [0, S), NULL =
+ * one segment — followed by the excluded ones; seg_ptr[S+1] the segments' first positions with
+ * seg_ptr[S] = m, the number of included elements (it stays on the device); flags[n] per position:
+ * bit 0 last of its tie group (bit-equal scores of one segment; -0.0 == +0.0), bit 1 first of its
+ * segment, bit 2 first of its tie group; rank[n] (optional) the inverse of order.  One stable radix
+ * sort of 64-bit (segment, inverted orderable score) keys over the bits in use.
+ */
+gnn_status gnn_rank_plan_workspace_size(int64_t n, int64_t num_segments, size_t* bytes);
+gnn_status gnn_rank_plan_build(const float* scores, const uint8_t* include, const int32_t* segment,
+                               int64_t n, int64_t num_segments, int32_t* order, uint8_t* flags,
+                               int32_t* seg_ptr, int32_t* rank, int32_t* status, void* workspace,
+                               size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * Per segment s of a plan: ap[s] = sum over tie groups g of (TP_g - TP_{g-1}) * TP_g / (TP_g + FP_g),
+ * over P (f64; 0 when P = 0 or the segment is empty), num_pos[s] = P, count[s] = elements, and with
+ * patk (optional; needs k >= 1) the mean of positive[] over the first min(k, count[s]) positions.
+ * positive[n] is indexed by element (non-zero = positive).  Integer counts, f64 terms summed in one
+ * fixed order: bitwise reproducible.
+ */
+gnn_status gnn_rank_ap_workspace_size(int64_t n, int64_t num_segments, size_t* bytes);
+gnn_status gnn_rank_ap(const int32_t* order, const uint8_t* flags, const int32_t* seg_ptr,
+                       const uint8_t* positive, int64_t n, int64_t num_segments, int64_t k, double* ap,
+                       int64_t* num_pos, int64_t* count, double* patk, void* workspace,
+                       size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * Paired bootstrap replicates: plans A and B of two score vectors over the same n elements (no mask,
+ * one segment) and sample_idx[num_replicates, n] (int32 in [0, n)).  Replicate r weighs element i by
+ * how often row r draws it; ap_x[r] is the weighted average precision (equal to the AP of the
+ * resampled arrays) and patk_x[r] the weighted precision at k (min(w_i, k - taken) copies per element
+ * in plan order).  num_replicates < 65536 per call; k >= 1.  n <= GNN_RANK_BOOT_LDS_MAX_N needs no
+ * workspace beyond the queried minimum.
+ */
+gnn_status gnn_rank_bootstrap_workspace_size(int64_t n, int64_t num_replicates, size_t* bytes);
+gnn_status gnn_rank_bootstrap(const int32_t* order_a, const int32_t* rank_a, const uint8_t* flags_a,
+                              const int32_t* order_b, const int32_t* rank_b, const uint8_t* flags_b,
+                              const uint8_t* positive, const int32_t* sample_idx, int64_t n,
+                              int64_t num_replicates, int64_t k, double* ap_a, double* ap_b,
+                              double* patk_a, double* patk_b, int32_t* status, void* workspace,
+                              size_t workspace_bytes, gnn_stream_t stream);
 
 #ifdef __cplusplus
 }
