@@ -201,6 +201,16 @@ struct TNArgs {
 // rows: 2 · ceil(ceil(M / 32) / 256) <= 392); at most one per thread of its 512
 constexpr int TN_ACT_CAP = 512;
 
+// the exact-f32 MFMA forms and the ordered slab reduce every TN ends with (gemm_f32.hip); the
+// host entry points that choose among all the launchers below are in gemm_dispatch.hip
+void launch_nt_f32(const NTArgs& a, int avec, hipStream_t st);  // avec: widest A row vector (4, 2, 1)
+void launch_tn_f32(const TNArgs& a, int nblk, hipStream_t st);
+constexpr int kRedOut = 16;  // float4 outputs per block of the reduce
+// out[j] = Σ_{b < nred} slab[b · stride + j], j < n_out; sq: the call's params when they ask for the
+// norm partials of out (sq_partial, ABI 20), else null
+void launch_slab_reduce(const float* slab, int64_t stride, int nred, float* out, int64_t n_out,
+                        const gnn_gemm_tn_params* sq, hipStream_t st);
+
 // split-bf16 ("x3": each f32 operand = hi + mid + lo bf16, 6 MFMA products) launchers,
 // defined in gemm_x3.hip.  Only the w1/w2 (in-place Linear weight) B form runs split.
 void launch_nt_x3(const NTArgs& a, void* ws, size_t ws_bytes, hipStream_t st);
@@ -277,9 +287,12 @@ __device__ __forceinline__ uint32_t h2_scale_pair(uint32_t h, float s) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_{(float)v[0] * s, (float)v[1] * s}, h2_));
 }
 
-// VALU kernels for the narrow output-layer shapes (gemm_skinny.hip).  launch_nt_skinny returns
-// false (launching nothing) when the shape/epilogue is outside its envelope.
-bool launch_nt_skinny(const NTArgs& a, hipStream_t st);
+// VALU kernels for the narrow output-layer shapes (gemm_skinny.hip).  nt_skinny_form: the form
+// whose envelope holds the shape / epilogue (N: Nc <= 8; K: k1 <= 8, k2 = 0), which
+// launch_nt_skinny launches.
+enum NTSkinny { SKINNY_NONE, SKINNY_N, SKINNY_K };
+NTSkinny nt_skinny_form(const NTArgs& a);
+void launch_nt_skinny(const NTArgs& a, hipStream_t st);
 int nt_skinny_k_blocks(const NTArgs& a);  // grid of the skinny-K form (its colsum_part rows); 0: not that form
 int tn_skinny_blocks(int64_t M);
 bool tn_skinny_ok(const TNArgs& a);

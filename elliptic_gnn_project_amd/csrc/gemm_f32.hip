@@ -20,7 +20,6 @@
 #include "common.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "gemm_common.hpp"
 
@@ -28,7 +27,6 @@ namespace gnnmp {
 namespace {
 
 constexpr int BNP = BN + 2;  // LDS pitch of the B tile: 2P = 4 mod 32 makes the transposed weight stores (8 lanes x float2 per row) conflict-free
-
 
 // Tiling parameters: KC = K depth per LDS chunk, TM = 32-row tiles per wave (block rows
 // BM = 4 waves x 32·TM), UNR = fully unroll full chunks.
@@ -463,15 +461,7 @@ void launch_nt2_b(const NTArgs& a, hipStream_t st) {
   else launch_nt2<AVEC, 1, KC, true, EXP, DEPTH>(a, st);
 }
 
-// The exact-f32 NT: 16-deep chunks, one chunk of loads in flight (r01 lab, the fastest of the
-// [k][n]-image, 32-deep-chunk and two-chunks-in-flight forms).
-template <int AVEC>
-void launch_nt_f32(const NTArgs& a, hipStream_t st) {
-  launch_nt2_b<AVEC, 16>(a, st);
-}
-
 // ------------------------------------------------------------------------------------ TN
-
 
 // slab layout: dW[Nr][Kc] | db[Nr] | dW2[nproj][Nr] | dzsum[nproj]
 //
@@ -693,7 +683,7 @@ __global__ __launch_bounds__(TN_THREADS) void gemm_tn_kernel(TNArgs a) {
 struct SqOut {
   float* part; const float* step; int64_t skip_lo, skip_hi;
 };
-constexpr int kRedOut = 16, kRedGrp = 16;
+constexpr int kRedGrp = 16;
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int64_t stride, int nblk,
                                                           float* __restrict__ out, int64_t n, SqOut sq = SqOut{}) {
   __shared__ float4 part[kRedGrp][kRedOut];
@@ -758,470 +748,22 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   }
 }
 
-// Blocks of the TN launches: at most 256 (one per CU), and no more than the 32-row chunks need at
-// the chunks-per-block that 256 blocks would take — every block has rows, so no block writes an
-// all-zero slab for the reduce to read back (a strong-scaling shard: 213 instead of 256 slabs at
-// 27,196 rows, -17 % of the slab traffic).
-int tn_blocks(int64_t M) {
-  const int64_t chunks = ceil_div(M, 32);
-  if (chunks <= 0) return 1;
-  const int64_t per = ceil_div(chunks, 256);
-  return (int)ceil_div(chunks, per);
-}
-// the largest M whose half-pair dz-form TN runs split-K block pairs (GNNMP_TN_KSPLIT_MAXM, A/B)
-static int64_t tn_ksplit_max_m() {
-  static const int64_t v = [] {
-    const char* e = std::getenv("GNNMP_TN_KSPLIT_MAXM");
-    return e ? std::atoll(e) : (int64_t)32768;  // the 8-way shard (27k rows): TN + reduce 32.1 -> 30.9 us; 4-way (52k): slower
-  }();
-  return v;
-}
-
-// (ABI 26) the CSC sum of u inside the half-pair dz-form TN when each of its 8 waves walks at most
-// one 64-row group of the block's rows (shard-sized M: 8-way shard 0.0947 -> 0.0923 ms per step,
-// profiles/r105_csc_ab.txt); GNNMP_TN_CSC_INKERNEL=0 / 1 forces it off / on (A/B)
-// rows per block of the half-pair TN (dz: the dz form, split-K pairs at shard-sized M)
-static int64_t tn_h2_rows_per_block(int64_t M, bool dz) {
-  const int64_t chunks = ceil_div(M, 32);
-  if (dz && M <= tn_ksplit_max_m()) return ceil_div(chunks, 128) * 32;
-  return ceil_div(chunks, tn_blocks(M)) * 32;
-}
-static bool tn_csc_in_kernel(int64_t rows_per_block) {
-  static const int v = [] {
-    const char* e = std::getenv("GNNMP_TN_CSC_INKERNEL");
-    return e ? std::atoi(e) : -1;
-  }();
-  if (rows_per_block > 1792) return false;  // the block's dz rows staged in LDS (gemm_planes.hip dzb)
-  if (v >= 0) return v != 0;
-  return (rows_per_block + 63) / 64 + 1 <= 8;  // groups a block's rows can touch <= its waves
-}
-
-// (ABI 28) whether the dz-form TN at M rows walks activity flags: its row block is larger than the
-// in-kernel CSC fold takes (tn_csc_in_kernel's shape rule, without the env override: a rule of M
-// alone, so the caller's CSC sum, the call-side one and GNNMP_TN_CSC=0 all reach the same kernel)
-static bool tn_active_pays(int64_t M) {
-  if (M < 16) return false;
-  const int64_t rpb = tn_h2_rows_per_block(M, true);
-  return (rpb + 63) / 64 + 1 > 8;
-}
-static int64_t tn_active_bytes(int64_t M) { return (ceil_div(M, GNN_ACTIVE_ROWS) + 15) / 16 * 16; }
-
-// the in-kernel half-pair TN at Nr <= 64, k1 + k2 <= 128 holds three blocks per CU (its LDS is
-// sized by its k-tiles and 64 G rows, 47 KB): three times the blocks, so three times the chunk loads
-// in flight per CU (its chunk loop is latency-bound: one 16-row chunk in flight per block)
-int tn_blocks2(int64_t M) {
-  const int64_t chunks = ceil_div(M, 32);
-  if (chunks <= 0) return 1;
-  const int64_t per = ceil_div(chunks, 768);
-  return (int)ceil_div(chunks, per);
-}
 
 }  // namespace
-}  // namespace gnnmp
 
-using namespace gnnmp;
-
-static gnn_status gemm_nt_dispatch(const gnn_gemm_nt_params* p, gnn_stream_t stream, const char* fn, int phase) {
-  if (!p) return fail(GNN_ERR_INVALID_ARG, fn, "null params");
-  if (phase == NT_PHASE_ALL && p->b_ready) phase = NT_PHASE_RUN;
-  const bool planes_only = p->a_planes && !p->a1;  // A given only as a split image
-  if (p->M < 0 || p->N < 1 || p->k1 < 1 || p->k2 < 0 || (!p->a1 && !p->a_planes) ||
-      (p->k2 > 0 && !p->a2 && !planes_only))
-    return fail(GNN_ERR_INVALID_ARG, fn, "bad shapes / null operands");
-  if (!p->bt && !(p->w1 && (p->k2 == 0 || p->w2)))
-    return fail(GNN_ERR_INVALID_ARG, fn, "need bt or w1 (and w2 when k2 > 0)");
-  if (p->w1 && (p->N > BN || p->ldw1 < p->k1 || (p->k2 > 0 && p->ldw2 < p->k2)))
-    return fail(GNN_ERR_INVALID_ARG, fn, "w1/w2 form needs N <= 128 and ldw >= k");
-  if ((!planes_only && (p->lda1 < p->k1 || (p->k2 > 0 && p->lda2 < p->k2))) || (p->bt && p->ldb < p->N) ||
-      (p->c && p->ldc < p->N))
-    return fail(GNN_ERR_INVALID_ARG, fn, "bad leading dimensions");
-  if (p->nproj < 0 || p->nproj > 4 || (p->nproj > 0 && (p->N > BN || !p->proj || !p->z || p->ldz < p->nproj)))
-    return fail(GNN_ERR_INVALID_ARG, fn, "projection needs N <= 128, nproj <= 4, proj and z");
-  if (p->dropout_p < 0.f || p->dropout_p >= 1.f) return fail(GNN_ERR_INVALID_ARG, fn, "dropout p in [0,1)");
-  if (p->dropout_p > 0.f && (int64_t)p->M * (int64_t)p->N >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, fn, "dropout element index (rows x width) must be < 2^32");
-  if (p->math != GNN_MATH_SPLIT_BF16 && p->math != GNN_MATH_F32 && p->math != GNN_MATH_HALF_PAIR)
-    return fail(GNN_ERR_INVALID_ARG, fn, "bad math mode");
-  if ((p->a_dtype != GNN_DTYPE_F32 && p->a_dtype != GNN_DTYPE_BF16) || (p->c_dtype != GNN_DTYPE_F32 && p->c_dtype != GNN_DTYPE_BF16))
-    return fail(GNN_ERR_INVALID_ARG, fn, "bad dtype");
-  if (p->row_exp && (p->a_planes || p->colsum_part || phase != NT_PHASE_ALL))
-    return fail(GNN_ERR_UNSUPPORTED, fn, "row_exp needs the in-kernel half-pair NT over f32 A1 / A2");
-  if (p->M == 0 && phase != NT_PHASE_PREP) return GNN_OK;
-  NTArgs a{};
-  a.M = p->M; a.Nc = (int32_t)p->N;
-  a.a1 = p->a1; a.lda1 = p->lda1; a.k1 = (int32_t)p->k1;
-  a.a2 = p->a2; a.lda2 = p->lda2; a.k2 = (int32_t)p->k2;
-  a.bt = p->bt; a.ldb = p->ldb; a.w1 = p->w1; a.w2 = p->w2; a.ldw1 = p->ldw1; a.ldw2 = p->ldw2; a.c = p->c;
-  a.ldc = p->ldc; a.bias = p->bias; a.relu = p->relu;
-  a.dropout = p->dropout_p > 0.f;
-  a.keep_thresh = (uint32_t)((1.0 - (double)p->dropout_p) * 16777216.0);
-  a.drop_scale = a.dropout ? (float)(1.0 / (1.0 - (double)p->dropout_p)) : 1.0f;
-  a.seed = p->seed;
-  a.seed_ptr = p->seed_ptr;
-  a.proj = p->proj; a.nproj = p->nproj; a.z = p->z; a.ldz = p->ldz;
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
-  a.wvec2 = a.w1 && (a.ldw1 % 2 == 0) && (a.k1 % 2 == 0) && al(a.w1, 8) &&
-            (a.k2 == 0 || ((a.ldw2 % 2 == 0) && (a.k2 % 2 == 0) && al(a.w2, 8)));
-  auto wv = [&](int v) {
-    return a.w1 && (a.ldw1 % v == 0) && (a.k1 % v == 0) && al(a.w1, 4 * v) &&
-           (a.k2 == 0 || ((a.ldw2 % v == 0) && (a.k2 % v == 0) && al(a.w2, 4 * v)));
-  };
-  a.wvec = wv(4) ? 4 : (wv(2) ? 2 : 1);
-  bool v4 = (a.k1 % 4 == 0) && (a.lda1 % 4 == 0) && al(a.a1, 16) &&
-            (a.k2 == 0 || ((a.k2 % 4 == 0) && (a.lda2 % 4 == 0) && al(a.a2, 16)));
-  bool v2 = (a.k1 % 2 == 0) && (a.lda1 % 2 == 0) && al(a.a1, 8) &&
-            (a.k2 == 0 || ((a.k2 % 2 == 0) && (a.lda2 % 2 == 0) && al(a.a2, 8)));
-  hipStream_t st = (hipStream_t)stream;
-  a.a_bf16 = p->a_dtype == GNN_DTYPE_BF16;
-  a.c_bf16 = p->c_dtype == GNN_DTYPE_BF16;
-  a.mask = p->mask; a.ldmask = p->ldmask; a.mask_scale = p->mask_scale;
-  if (p->mask && p->ldmask < p->N) return fail(GNN_ERR_INVALID_ARG, fn, "bad ldmask");
-  if (p->colsum_part) {  // ABI 21: the skinny-K form also writes C's per-block column sums
-    const int nb = nt_skinny_k_blocks(a);
-    if (nb == 0 || p->a_planes || phase != NT_PHASE_ALL)
-      return fail(GNN_ERR_UNSUPPORTED, fn, "colsum_part needs the skinny-K form (k1 <= 8, k2 = 0, 8 < N <= 256)");
-    if (p->colsum_cap < (int64_t)nb * p->N || (reinterpret_cast<uintptr_t>(p->colsum_part) & 3))
-      return fail(GNN_ERR_INVALID_ARG, fn, "colsum_cap < gnn_gemm_nt_colsum_blocks x N");
-    a.colsum_part = p->colsum_part;
-    if (!launch_nt_skinny(a, st)) return fail(GNN_ERR_UNSUPPORTED, fn, "colsum_part: not the skinny-K form");
-    return hip_check(hipGetLastError(), fn);
-  }
-  if (p->a_planes) {
-    if (p->planes_format != GNN_PLANES_SPLIT_BF16 && p->planes_format != GNN_PLANES_HALF_PAIR)
-      return fail(GNN_ERR_INVALID_ARG, fn, "bad planes_format");
-    a.ap = static_cast<const uint16_t*>(p->a_planes);
-    a.ap_ld = (int32_t)std::min<int64_t>(p->planes_ld, INT32_MAX);
-    a.ap_col2 = (int32_t)std::min<int64_t>(p->planes_col2, INT32_MAX);
-    a.ap_ps = p->planes_stride;
-    a.ap_h2 = p->planes_format == GNN_PLANES_HALF_PAIR;
-    a.ap_exp = a.ap_h2 ? p->planes_exp : 0;
-    if (a.ap_exp < -100 || a.ap_exp > 100) return fail(GNN_ERR_INVALID_ARG, fn, "planes_exp outside [-100, 100]");
-    const size_t img_bytes = (size_t)(a.ap_ld / 16) * 3 * 256 * sizeof(uint4);
-    if (p->keep_mask) {
-      if (!a.ap_h2 || !a.dropout || (reinterpret_cast<uintptr_t>(p->keep_mask) & 3))
-        return fail(GNN_ERR_INVALID_ARG, fn, "keep_mask needs a half-pair image A and dropout_p > 0");
-      a.kmask = p->keep_mask;
-    }
-    if (a.ap_h2) {  // the half-pair image: f16 hi / lo planes, 3 products
-      if (p->math != GNN_MATH_F32 && !p->mask && nt_h2_ok(a) && p->workspace &&
-          p->workspace_bytes >= img_bytes + BN * sizeof(float)) {
-        launch_nt_h2(a, static_cast<uint4*>(p->workspace), st, phase);
-        return hip_check(hipGetLastError(), fn);
-      }
-      if (planes_only) return fail(GNN_ERR_UNSUPPORTED, fn, "half-pair image A outside the half-pair kernel's shapes");
-      a.ap = nullptr;
-    }
-    if (a.a_bf16) {  // a bf16 image (one plane): the bf16-storage form
-      if (p->math != GNN_MATH_F32 && !p->mask && nt_img16_ok(a) && p->workspace && p->workspace_bytes >= img_bytes) {
-        launch_nt_img16(a, static_cast<uint4*>(p->workspace), st, phase);
-        return hip_check(hipGetLastError(), fn);
-      }
-      return fail(GNN_ERR_UNSUPPORTED, fn, "bf16 image A outside the image kernel's shapes");
-    }
-    if (p->math != GNN_MATH_F32 && !p->mask && nt_planes_ok(a) && p->workspace &&
-        p->workspace_bytes >= img_bytes) {
-      launch_nt_ws_planes(a, static_cast<uint4*>(p->workspace), st, phase);
-      return hip_check(hipGetLastError(), fn);
-    }
-    if (planes_only) return fail(GNN_ERR_UNSUPPORTED, fn, "split-image A outside the planes kernel's shapes");
-    a.ap = nullptr;  // the f32 operands serve
-  }
-  if (phase != NT_PHASE_ALL)  // prep_b / b_ready: only the image-A kernels have a separate B image
-    return fail(phase == NT_PHASE_PREP ? GNN_ERR_UNSUPPORTED : GNN_ERR_INVALID_ARG, fn,
-                "a separate B prep (prep_b / b_ready) needs an image-A kernel (gnn_gemm_nt_planes_ok)");
-  const bool h2s = p->math == GNN_MATH_HALF_PAIR && nt_h2s_ok(a) && p->workspace &&
-                   p->workspace_bytes >= nt_h2s_workspace(a.k1, a.k2);
-  if (p->row_exp && !h2s)  // (checked before the skinny forms: a caller asking for row_exp gets it or an error)
-    return fail(GNN_ERR_UNSUPPORTED, fn, "row_exp needs the in-kernel half-pair NT (GNN_MATH_HALF_PAIR, the w1/w2 "
-                                         "form, N <= 128, k1 / k2 multiples of 16, k1 + k2 <= 128, f32, a workspace)");
-  if (!p->row_exp && launch_nt_skinny(a, st)) return hip_check(hipGetLastError(), fn);  // Nc <= 8 or K <= 8
-  if (p->mask) return fail(GNN_ERR_UNSUPPORTED, fn, "the mask epilogue needs a skinny shape (K <= 8 or N <= 8)");
-  if (a.a_bf16 || a.c_bf16) {
-    if (!a.a_bf16 || !a.w1 || a.Nc > BN || p->math == GNN_MATH_F32)
-      return fail(GNN_ERR_UNSUPPORTED, fn, "bf16 NT needs bf16 A, the w1/w2 form, N <= 128 and split math");
-    launch_nt_x3(a, p->workspace, p->workspace_bytes, st);
-    return hip_check(hipGetLastError(), fn);
-  }
-  if (h2s) {  // in-kernel half-pair (gemm_x3.hip, ABI 23)
-    a.rowexp = p->row_exp;
-    launch_nt_h2s(a, p->workspace, st);
-    return hip_check(hipGetLastError(), fn);
-  }
-  if (p->math != GNN_MATH_F32 && a.w1 && a.Nc <= BN) {
-    launch_nt_x3(a, p->workspace, p->workspace_bytes, st);  // split-bf16 MFMA (gemm_x3.hip)
-    return hip_check(hipGetLastError(), fn);
-  }
-  if (v4) launch_nt_f32<4>(a, st);
-  else if (v2) launch_nt_f32<2>(a, st);
-  else launch_nt_f32<1>(a, st);
-  return hip_check(hipGetLastError(), fn);
+// The exact-f32 NT: 16-deep chunks, one chunk of loads in flight (r01 lab, the fastest of the
+// [k][n]-image, 32-deep-chunk and two-chunks-in-flight forms).
+void launch_nt_f32(const NTArgs& a, int avec, hipStream_t st) {
+  if (avec == 4) launch_nt2_b<4, 16>(a, st);
+  else if (avec == 2) launch_nt2_b<2, 16>(a, st);
+  else launch_nt2_b<1, 16>(a, st);
 }
 
-extern "C" gnn_status gnn_gemm_nt_workspace_size(int64_t N, int64_t k1, int64_t k2, size_t* bytes) {
-  if (!bytes || N < 1 || k1 < 1 || k2 < 0) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
-  // the image-A kernels (a_planes) size their B image by the image's row width (<= 336 columns,
-  // 21 k-steps), not by k1 + k2: a narrow input on a 176-wide image runs 11 k-steps
-  *bytes = N <= BN ? std::max(nt_x3_workspace(k1, k2), (size_t)21 * 3 * 256 * 16 + BN * sizeof(float)) : 0;
-  return GNN_OK;
-}
-
-extern "C" gnn_status gnn_gemm_nt_f32(const gnn_gemm_nt_params* p, gnn_stream_t stream) {
-  return gemm_nt_dispatch(p, stream, __func__, NT_PHASE_ALL);
-}
-
-extern "C" gnn_status gnn_gemm_nt_prep_b(const gnn_gemm_nt_params* p, gnn_stream_t stream) {
-  return gemm_nt_dispatch(p, stream, __func__, NT_PHASE_PREP);
-}
-
-
-extern "C" gnn_status gnn_gemm_tn_workspace_size(int64_t M, int64_t Nr, int64_t Kc, int32_t nproj, size_t* bytes) {
-  if (!bytes || M < 0 || Nr < 1 || Kc < 1 || nproj < 0) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
-  int64_t stride = Nr * Kc + Nr + (int64_t)nproj * Nr + nproj;
-  stride = (stride + 63) / 64 * 64;
-  int64_t nb = tn_blocks(M);
-  if (Nr <= 8 && nproj == 0) nb = std::max<int64_t>(nb, tn_skinny_blocks(M));  // gemm_skinny.hip
-  if (Nr <= 64 && Kc <= 128 && nproj == 0) nb = std::max<int64_t>(nb, tn_blocks2(M));  // the narrow half-pair TN
-  *bytes = (size_t)nb * stride * sizeof(float);
-  // (ABI 28) the call-side CSC sum's activity flags, past the slabs of tn_blocks(M) blocks
-  if (nproj > 0 && tn_active_pays(M)) *bytes += (size_t)tn_active_bytes(M);
-  return GNN_OK;
-}
-
-extern "C" int gnn_gemm_tn_active_pays(int64_t M) { return tn_active_pays(M) ? 1 : 0; }
-
-static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* workspace,
-                                   size_t workspace_bytes, gnn_stream_t stream, const uint8_t* dz_active = nullptr);
-
-// (ABI 26) the folded CSC sum's arguments (dz_graph's CSC, dz_u, dz_cols); false when dz_graph is
-// given but cannot be taken (no dz form, no u, dz_cols outside 1..min(2, nproj), num_nodes != M)
-static bool tn_csc_args(const gnn_gemm_tn_params* p, TNArgs* a) {
-  a->cptr = nullptr; a->cnbr = nullptr; a->cu = nullptr; a->ldu = 0; a->ccols = 0;
-  const gnn_graph* cg = p->dz_graph;
-  if (!cg) return true;
-  if (!p->dz || !p->dz_u || !cg->colptr || !cg->row || cg->num_nodes != p->M || p->dz_cols < 1 || p->dz_cols > 2 ||
-      p->dz_cols > p->nproj || p->ldu < p->dz_cols)
-    return false;
-  a->cptr = cg->colptr; a->cnbr = cg->row; a->cu = p->dz_u; a->ldu = p->ldu; a->ccols = p->dz_cols;
-  return true;
-}
-
-static unsigned red_blocks(int64_t n_out) { return (unsigned)ceil_div(ceil_div(n_out, 4), kRedOut); }
-
-extern "C" gnn_status gnn_gemm_tn_sq_blocks(int64_t n_out, int32_t* nb) {
-  if (!nb || n_out < 1) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
-  *nb = (int32_t)red_blocks(n_out);
-  return GNN_OK;
-}
-
-extern "C" gnn_status gnn_gemm_tn_f32(const gnn_gemm_tn_params* p, float* out, void* workspace,
-                                      size_t workspace_bytes, gnn_stream_t stream) {
-  return gemm_tn_dispatch(p, out, workspace, workspace_bytes, stream);
-}
-
-extern "C" gnn_status gnn_gemm_tn_active_f32(const gnn_gemm_tn_params* p, const uint8_t* dz_active, float* out,
-                                             void* workspace, size_t workspace_bytes, gnn_stream_t stream) {
-  return gemm_tn_dispatch(p, out, workspace, workspace_bytes, stream, dz_active);
-}
-
-
-static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* workspace,
-                                   size_t workspace_bytes, gnn_stream_t stream, const uint8_t* dz_active) {
-  const char* __fn = dz_active ? "gnn_gemm_tn_active_f32" : "gnn_gemm_tn_f32";
-  if (!p || !out) return fail(GNN_ERR_INVALID_ARG, __fn, "null params/out");
-  // (ABI 28) flags: the half-pair dz form with h, no gout, no dz_graph (checked again with the
-  // image's shape below) — refused here, before any launch
-  if (dz_active) {
-    if (!p->dz || !p->h || p->gout || p->dz_graph || !p->a_planes || p->planes_format != GNN_PLANES_HALF_PAIR ||
-        p->math == GNN_MATH_F32 || p->M < 16)
-      return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active needs the half-pair dz form with h, no gout, no dz_graph, M >= 16");
-    if (reinterpret_cast<uintptr_t>(dz_active) & 15) return fail(GNN_ERR_INVALID_ARG, __fn, "dz_active must be 16-byte aligned");
-  }
-  if (p->M < 0 || p->Nr < 1 || p->Nr > 128 || p->k1 < 1 || p->k2 < 0 || p->k1 + p->k2 > KMAX)
-    return fail(GNN_ERR_UNSUPPORTED, __fn, "needs 1 <= Nr <= 128 and k1 + k2 <= 384");
-  const bool planes_only = p->a_planes && !p->a1;
-  if (!planes_only && (!p->a1 || (p->k2 > 0 && !p->a2) || p->lda1 < p->k1 || (p->k2 > 0 && p->lda2 < p->k2)))
-    return fail(GNN_ERR_INVALID_ARG, __fn, "bad A operands");
-  if (p->dz) {
-    if (p->nproj < 1 || p->nproj > MAXPROJ || !p->proj || p->lddz < p->nproj)
-      return fail(GNN_ERR_INVALID_ARG, __fn, "dz form needs 1 <= nproj <= 4 and proj");
-  } else if (!p->g || p->ldg < p->Nr) {
-    return fail(GNN_ERR_INVALID_ARG, __fn, "need g (or dz + proj)");
-  }
-  if (p->h && p->ldh < p->Nr) return fail(GNN_ERR_INVALID_ARG, __fn, "bad ldh");
-  if (p->math != GNN_MATH_SPLIT_BF16 && p->math != GNN_MATH_F32 && p->math != GNN_MATH_HALF_PAIR)
-    return fail(GNN_ERR_INVALID_ARG, __fn, "bad math mode");
-  if (p->gout && p->ldgout < p->Nr) return fail(GNN_ERR_INVALID_ARG, __fn, "bad ldgout");
-  const int32_t nproj = p->dz ? p->nproj : 0;
-  const int64_t Kc = p->k1 + p->k2;
-  const int64_t n_out = p->Nr * Kc + p->Nr + (int64_t)nproj * p->Nr + nproj;
-  int64_t stride = (n_out + 63) / 64 * 64;
-  int nblk = tn_blocks(p->M);
-  if (!workspace || workspace_bytes < (size_t)nblk * stride * sizeof(float))
-    return fail(GNN_ERR_WORKSPACE, __fn, "workspace too small");
-  hipStream_t st = (hipStream_t)stream;
-  SqOut sqo{};
-  if (p->sq_partial) {
-    if (!p->sq_step || p->sq_cap < 2 * (int64_t)red_blocks(n_out) + 1 || p->sq_skip_lo > p->sq_skip_hi)
-      return fail(GNN_ERR_INVALID_ARG, __fn, "sq_partial needs sq_step, sq_cap >= 2 nb + 1, skip_lo <= skip_hi");
-    sqo = SqOut{p->sq_partial, p->sq_step, p->sq_skip_lo, p->sq_skip_hi};
-  }
-  if (p->M == 0) {
-    if (!p->sq_partial) return hip_check(hipMemsetAsync(out, 0, n_out * sizeof(float), st), __fn);
-    slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(static_cast<float*>(workspace), stride, 0, out, n_out, sqo);
-    return hip_check(hipGetLastError(), __fn);  // zero slabs: out = 0, partials 0, the step snapshot
-  }
-  TNArgs a{};
-  a.M = p->M; a.Nr = (int32_t)p->Nr;
-  a.g = p->g; a.ldg = p->ldg; a.dz = p->dz; a.lddz = p->lddz; a.proj = p->proj; a.nproj = nproj;
-  a.h = p->h; a.ldh = p->ldh; a.hscale = p->hscale;
-  a.gout = p->gout; a.ldgout = p->ldgout;
-  a.a1 = p->a1; a.lda1 = p->lda1; a.k1 = (int32_t)p->k1;
-  a.a2 = p->a2; a.lda2 = p->lda2; a.k2 = (int32_t)p->k2;
-  a.slab = static_cast<float*>(workspace); a.slab_stride = stride;
-  a.rows_per_block = ceil_div(ceil_div(p->M, 32), nblk) * 32;  // multiple of both chunk sizes
-  if (!tn_csc_args(p, &a))
-    return fail(GNN_ERR_INVALID_ARG, __fn, "dz_graph needs the dz form, dz_u, 1 <= dz_cols <= 2 and num_nodes == M");
+void launch_tn_f32(const TNArgs& a, int nblk, hipStream_t st) {
   auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; };
   const bool v2 = (a.k1 % 2 == 0) && (a.lda1 % 2 == 0) && al8(a.a1) &&
                   (a.k2 == 0 || ((a.k2 % 2 == 0) && (a.lda2 % 2 == 0) && al8(a.a2)));
   const bool proj = a.dz != nullptr, mask = a.h != nullptr;
-  a.a_bf16 = p->a_dtype == GNN_DTYPE_BF16;
-  a.h_bf16 = p->h_dtype == GNN_DTYPE_BF16;
-  a.g_bf16 = p->g_dtype == GNN_DTYPE_BF16;
-  if ((p->a_dtype != GNN_DTYPE_F32 && p->a_dtype != GNN_DTYPE_BF16) || (p->h_dtype != GNN_DTYPE_F32 && p->h_dtype != GNN_DTYPE_BF16) ||
-      (p->g_dtype != GNN_DTYPE_F32 && p->g_dtype != GNN_DTYPE_BF16))
-    return fail(GNN_ERR_INVALID_ARG, __fn, "bad dtype");
-  if (a.g_bf16 && !(p->a_planes && a.a_bf16))
-    return fail(GNN_ERR_UNSUPPORTED, __fn, "bf16 g / gout need the bf16-image TN (a bf16 a_planes)");
-  if (a.h_bf16 && !a.a_bf16) return fail(GNN_ERR_UNSUPPORTED, __fn, "bf16 h needs bf16 A");
-  // widest row pitch of any operand (the split kernel uses 32-bit element offsets)
-  const int64_t ldmax = std::max({a.lda1, a.k2 > 0 ? a.lda2 : 0, a.h ? a.ldh : 0, a.g ? a.ldg : 0, a.dz ? a.lddz : 0});
-  if (p->a_planes) {
-    if (p->planes_format != GNN_PLANES_SPLIT_BF16 && p->planes_format != GNN_PLANES_HALF_PAIR)
-      return fail(GNN_ERR_INVALID_ARG, __fn, "bad planes_format");
-    a.ap = static_cast<const uint16_t*>(p->a_planes);
-    a.ap_ld = (int32_t)std::min<int64_t>(p->planes_ld, INT32_MAX);
-    a.ap_col2 = (int32_t)std::min<int64_t>(p->planes_col2, INT32_MAX);
-    a.ap_ps = p->planes_stride;
-    a.ap_h2 = p->planes_format == GNN_PLANES_HALF_PAIR;
-    a.ap_exp = a.ap_h2 ? p->planes_exp : 0;
-    if (a.ap_exp < -100 || a.ap_exp > 100) return fail(GNN_ERR_INVALID_ARG, __fn, "planes_exp outside [-100, 100]");
-    if (a.ap_h2) {  // the half-pair image: f16 hi / lo planes, 3 products
-      // (ABI 25) the plain g form's block scale from the producer's row-group maxima (row blocks are
-      // whole 32-row chunks, so every block covers whole GNN_ROWMAX_ROWS groups)
-      a.growmax = (!a.dz && a.g) ? p->g_rowmax : nullptr;
-      if (dz_active && !(tn_h2_ok(a) && a.dz && !a.gout && !a.cptr))
-        return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active outside the half-pair dz-form TN's shapes");
-      if (p->math != GNN_MATH_F32 && tn_h2_ok(a)) {
-        // (ABI 28) the call-side CSC sum below also writes dz's activity flags (past the slabs) where
-        // they pay, and the TN walks them: the same kernel the caller's own flagged CSC sum reaches
-        const bool call_side = a.cptr && !tn_csc_in_kernel(tn_h2_rows_per_block(a.M, true));
-        uint8_t* ws_flags = nullptr;
-        if (call_side && tn_active_pays(a.M)) {
-          const size_t off = (size_t)nblk * stride * sizeof(float);
-          if (workspace_bytes < off + (size_t)tn_active_bytes(a.M) || (reinterpret_cast<uintptr_t>(workspace) & 15))
-            return fail(GNN_ERR_WORKSPACE, __fn, "workspace too small for the activity flags (gnn_gemm_tn_workspace_size)");
-          ws_flags = static_cast<uint8_t*>(workspace) + off;
-        }
-        a.dz_active = dz_active ? dz_active : ws_flags;
-        // a shard-sized M (the dz form): split-K block pairs over half as many row blocks (round 6).
-        // The flag-driven kernel never splits K, but it runs the row blocks of the dense call at the
-        // same M (nred of them, rows_per_block each), so its sums are the dense call's, bit for bit
-        int nred = nblk;
-        const bool ksr = a.dz && a.M <= tn_ksplit_max_m();
-        const bool ks = ksr && !a.dz_active;
-        if (ksr) {
-          const int64_t chunks = ceil_div(a.M, 32), per = ceil_div(chunks, 128);
-          nred = (int)ceil_div(chunks, per);
-          a.rows_per_block = per * 32;
-        }
-        if (a.rows_per_block != tn_h2_rows_per_block(a.M, a.dz != nullptr))
-          return fail(GNN_ERR_HIP, __fn, "internal: TN row-block rule mismatch");
-        if (a.dz_active) {  // the block's chunk list is a fixed array
-          if (a.rows_per_block / GNN_ACTIVE_ROWS > TN_ACT_CAP)
-            return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_active: row block beyond the chunk list's capacity");
-        }
-        if (a.cptr && !tn_csc_in_kernel(a.rows_per_block)) {
-          // (ABI 26) rows of more than one 64-row group per wave: the folded CSC sum would run two
-          // dependent gather rounds per wave ahead of the chunk loop (full configs[1] graph, 800 rows a
-          // block: TN 87 -> 94 us, profiles/r105_csc_ab.txt) — the separate narrow launch instead
-          gnn_agg_params ag{};
-          ag.mode = GNN_AGG_SUM;
-          ag.transpose = 1;
-          gnn_agg_active act{};
-          act.row_active = ws_flags;
-          act.active_with = p->dz + p->dz_cols;
-          act.ld_active_with = p->lddz;
-          act.active_with_cols = nproj - p->dz_cols;
-          const gnn_status s = gnn_aggregate_active_f32(p->dz_graph, &ag, p->dz_u, p->ldu, p->dz_cols,
-                                                        const_cast<float*>(p->dz), p->lddz, &act, stream);
-          if (s != GNN_OK) return s;
-          a.cptr = nullptr;
-        }
-        launch_tn_h2(a, ks ? 2 * nred : nred, st, ks);
-        GNN_LAUNCH_CHECK();
-        slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nred, out, n_out, sqo);
-        GNN_LAUNCH_CHECK();
-        return GNN_OK;
-      }
-      if (planes_only) return fail(GNN_ERR_UNSUPPORTED, __fn, "half-pair image A outside the half-pair kernel's shapes");
-      a.ap = nullptr;
-    }
-  }
-  if (a.cptr)  // only the half-pair dz-form kernel forms dz's CSC columns itself
-    return fail(GNN_ERR_UNSUPPORTED, __fn, "dz_graph outside the half-pair dz-form TN (gnn_gemm_tn_planes_ok)");
-  if (p->a_planes) {
-    if (a.ap && a.a_bf16) {  // a bf16 image (one plane): the bf16-storage form
-      if (p->math == GNN_MATH_F32 || !tn_img16_ok(a))
-        return fail(GNN_ERR_UNSUPPORTED, __fn, "bf16 image A outside the image kernel's shapes");
-      launch_tn_img16(a, nblk, st);
-      GNN_LAUNCH_CHECK();
-      slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-      GNN_LAUNCH_CHECK();
-      return GNN_OK;
-    }
-    if (a.ap && p->math != GNN_MATH_F32 && tn_planes_ok(a)) {
-      launch_tn_planes(a, nblk, st);
-      GNN_LAUNCH_CHECK();
-      slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-      GNN_LAUNCH_CHECK();
-      return GNN_OK;
-    }
-    if (planes_only) return fail(GNN_ERR_UNSUPPORTED, __fn, "split-image A outside the planes kernel's shapes");
-    a.ap = nullptr;
-  }
-  if (tn_skinny_ok(a)) {  // Nr <= 8 plain g form: VALU stream (gemm_skinny.hip)
-    nblk = tn_skinny_blocks(a.M);
-    if (workspace_bytes < (size_t)nblk * stride * sizeof(float))
-      return fail(GNN_ERR_WORKSPACE, __fn, "workspace too small");
-    launch_tn_skinny(a, nblk, st);
-    GNN_LAUNCH_CHECK();
-    slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-    GNN_LAUNCH_CHECK();
-    return GNN_OK;
-  }
-  // the split kernel indexes rows with 32-bit element offsets and loads whole 16-row chunks
-  if (a.a_bf16 && (p->math == GNN_MATH_F32 || (a.M + 32) * ldmax >= ((int64_t)1 << 31) || a.M < 16))
-    return fail(GNN_ERR_UNSUPPORTED, __fn, "bf16 TN needs split math, M >= 16 and M*ld < 2^31");
-  a.rowexp = p->row_exp;
-  if (p->math == GNN_MATH_HALF_PAIR && tn_h2s_ok(a) && (a.M + 32) * ldmax < ((int64_t)1 << 31)) {
-    if (a.Nr <= 64 && Kc <= 128 && !nproj && workspace_bytes >= (size_t)tn_blocks2(a.M) * stride * sizeof(float)) {
-      nblk = tn_blocks2(a.M);
-      a.rows_per_block = ceil_div(ceil_div(a.M, 32), nblk) * 32;
-    }
-    launch_tn_h2s(a, nblk, st);  // in-kernel half-pair MFMA (gemm_x3.hip, ABI 23)
-    GNN_LAUNCH_CHECK();
-    slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-    GNN_LAUNCH_CHECK();
-    return GNN_OK;
-  }
-  if (p->math != GNN_MATH_F32 && (a.M + 32) * ldmax < ((int64_t)1 << 31) && a.M >= 16) {
-    launch_tn_x3(a, nblk, st);  // split-bf16 MFMA (gemm_x3.hip)
-    GNN_LAUNCH_CHECK();
-    slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-    GNN_LAUNCH_CHECK();
-    return GNN_OK;
-  }
 #define GNN_TN(P, MK, V, R) gemm_tn_kernel<P, MK, V, R><<<nblk, TN_THREADS, 0, st>>>(a)
   // the dz·P + mask prologue holds twice the staging registers: 16-row chunks keep it spill-free
   if (proj && mask) { if (v2) GNN_TN(true, true, 2, 16); else GNN_TN(true, true, 1, 16); }
@@ -1229,77 +771,12 @@ static gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void
   else if (mask) { if (v2) GNN_TN(false, true, 2, 32); else GNN_TN(false, true, 1, 32); }
   else { if (v2) GNN_TN(false, false, 2, 32); else GNN_TN(false, false, 1, 32); }
 #undef GNN_TN
-  GNN_LAUNCH_CHECK();
-  slab_reduce_kernel<<<red_blocks(n_out), 256, 0, st>>>(a.slab, stride, nblk, out, n_out, sqo);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
 }
 
-// Whether a call would run the split-image kernels (the caller then needs no f32 A).
-static NTArgs nt_image_args(const gnn_gemm_nt_params* p) {  // the fields the image-A predicates read
-  NTArgs a{};
-  a.M = p->M; a.Nc = (int32_t)p->N; a.k1 = (int32_t)p->k1; a.k2 = (int32_t)p->k2;
-  a.w1 = p->w1; a.w2 = p->w2; a.ldw1 = p->ldw1; a.ldw2 = p->ldw2;
-  a.c = p->c; a.ldc = p->ldc; a.bias = p->bias; a.relu = p->relu;
-  a.dropout = p->dropout_p > 0.f; a.nproj = p->nproj; a.ldz = p->ldz;
-  a.a_bf16 = p->a_dtype == GNN_DTYPE_BF16; a.c_bf16 = p->c_dtype == GNN_DTYPE_BF16;
-  a.ap = static_cast<const uint16_t*>(p->a_planes);
-  a.ap_ld = (int32_t)std::min<int64_t>(p->planes_ld, INT32_MAX);
-  a.ap_col2 = (int32_t)std::min<int64_t>(p->planes_col2, INT32_MAX);
-  a.ap_ps = p->planes_stride;
-  a.ap_h2 = p->planes_format == GNN_PLANES_HALF_PAIR;
-  a.ap_exp = a.ap_h2 ? p->planes_exp : 0;
-  return a;
+void launch_slab_reduce(const float* slab, int64_t stride, int nred, float* out, int64_t n_out,
+                        const gnn_gemm_tn_params* sq, hipStream_t st) {
+  const SqOut sqo = sq && sq->sq_partial ? SqOut{sq->sq_partial, sq->sq_step, sq->sq_skip_lo, sq->sq_skip_hi} : SqOut{};
+  slab_reduce_kernel<<<(unsigned)ceil_div(ceil_div(n_out, 4), kRedOut), 256, 0, st>>>(slab, stride, nred, out, n_out, sqo);
 }
 
-extern "C" gnn_status gnn_gemm_nt_colsum_blocks(const gnn_gemm_nt_params* p, int32_t* nb) {
-  if (!p || !nb) return fail(GNN_ERR_INVALID_ARG, __func__, "null");
-  NTArgs a = nt_image_args(p);
-  *nb = p->a_planes ? 0 : nt_skinny_k_blocks(a);
-  return GNN_OK;
-}
-
-extern "C" int gnn_gemm_nt_planes_ok(const gnn_gemm_nt_params* p) {
-  if (!p || !p->a_planes || p->math == GNN_MATH_F32 || p->mask || p->M < 1) return 0;
-  const NTArgs a = nt_image_args(p);
-  if (a.ap_h2) return nt_h2_ok(a) ? 1 : 0;
-  return (a.a_bf16 ? nt_img16_ok(a) : nt_planes_ok(a)) ? 1 : 0;
-}
-
-namespace gnnmp {
-gnn_status nt_h2_prep_from_params(const gnn_gemm_nt_params* p, H2Prep* out, const char* fn) {
-  if (!p || !p->a_planes || p->math == GNN_MATH_F32 || p->mask || p->M < 1 || p->planes_format != GNN_PLANES_HALF_PAIR)
-    return fail(GNN_ERR_UNSUPPORTED, fn, "prep_b needs NT params that select the half-pair NT");
-  const NTArgs a = nt_image_args(p);
-  const size_t img_bytes = (size_t)(a.ap_ld / 16) * 3 * 256 * sizeof(uint4);
-  if (a.ap_exp < -100 || a.ap_exp > 100) return fail(GNN_ERR_INVALID_ARG, fn, "planes_exp outside [-100, 100]");
-  if (!nt_h2_ok(a) || !p->workspace || p->workspace_bytes < img_bytes + BN * sizeof(float) ||
-      (reinterpret_cast<uintptr_t>(p->workspace) & 15))
-    return fail(GNN_ERR_UNSUPPORTED, fn, "prep_b needs NT params that select the half-pair NT (and its workspace)");
-  *out = h2_prep_of(a, static_cast<uint4*>(p->workspace));
-  return GNN_OK;
-}
 }  // namespace gnnmp
-
-extern "C" int gnn_gemm_tn_planes_ok(const gnn_gemm_tn_params* p) {
-  if (!p || !p->a_planes || p->math == GNN_MATH_F32 || p->M < 1 || p->Nr < 1 || p->Nr > 128) return 0;
-  TNArgs a{};
-  a.M = p->M; a.Nr = (int32_t)p->Nr; a.g = p->g; a.ldg = p->ldg; a.dz = p->dz; a.lddz = p->lddz;
-  a.h = p->h; a.ldh = p->ldh; a.gout = p->gout; a.ldgout = p->ldgout; a.k1 = (int32_t)p->k1; a.k2 = (int32_t)p->k2;
-  a.a_bf16 = p->a_dtype == GNN_DTYPE_BF16; a.h_bf16 = p->h_dtype == GNN_DTYPE_BF16;
-  a.g_bf16 = p->g_dtype == GNN_DTYPE_BF16;
-  a.ap = static_cast<const uint16_t*>(p->a_planes);
-  a.ap_ld = (int32_t)std::min<int64_t>(p->planes_ld, INT32_MAX);
-  a.ap_col2 = (int32_t)std::min<int64_t>(p->planes_col2, INT32_MAX);
-  a.ap_ps = p->planes_stride;
-  a.ap_h2 = p->planes_format == GNN_PLANES_HALF_PAIR;
-  if (!tn_csc_args(p, &a)) return 0;
-  if (a.ap_h2) {
-    a.proj = p->proj; a.nproj = p->dz ? p->nproj : 0;
-    // (ABI 26) with dz_graph: 1 only when the kernel forms dz's CSC columns itself (a shard-sized
-    // row block); the call would otherwise launch the CSC sum first, which the caller can as well
-    if (a.cptr && !tn_csc_in_kernel(tn_h2_rows_per_block(a.M, true))) return 0;
-    return tn_h2_ok(a) ? 1 : 0;
-  }
-  return (!a.cptr && (a.a_bf16 ? tn_img16_ok(a) : tn_planes_ok(a))) ? 1 : 0;
-}

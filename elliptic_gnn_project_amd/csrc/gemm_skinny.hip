@@ -266,24 +266,31 @@ unsigned grid_for(int64_t M, int rpb, int64_t cap) {
 
 }  // namespace
 
-// the skinny-K form's VEC and grid (launch_nt_skinny below); 0 blocks: not that form
+// the skinny-K form's VEC (launch_nt_skinny below)
 static int skk_vec(const NTArgs& a) {
   auto c_ok = [&](int v) { return a.Nc % v == 0 && (!a.c || (a.ldc % v == 0 && al(a.c, 4 * v))); };
   return c_ok(4) ? 4 : (c_ok(2) ? 2 : 1);
 }
+
+// which skinny NT takes the call, launching nothing (the column sums ride only in the skinny-K form)
+NTSkinny nt_skinny_form(const NTArgs& a) {
+  if (a.a_bf16 || a.c_bf16 || a.nproj > 0 || a.M == 0) return SKINNY_NONE;
+  if (a.Nc <= SK_MAXN && a.k1 + a.k2 <= SK_KMAX) return a.colsum_part ? SKINNY_NONE : SKINNY_N;
+  if (a.k2 == 0 && a.k1 <= SK_MAXN && a.Nc <= 64 * 4 && lg2ceil((a.Nc + skk_vec(a) - 1) / skk_vec(a)) <= 8)
+    return SKINNY_K;
+  return SKINNY_NONE;
+}
+
 int nt_skinny_k_blocks(const NTArgs& a) {
-  if (a.a_bf16 || a.c_bf16 || a.nproj > 0 || a.M == 0 || a.Nc <= SK_MAXN) return 0;
-  if (!(a.k2 == 0 && a.k1 <= SK_MAXN && a.Nc <= 64 * 4)) return 0;
+  if (nt_skinny_form(a) != SKINNY_K) return 0;
   const int lg = lg2ceil((a.Nc + skk_vec(a) - 1) / skk_vec(a));
-  if (lg > 8) return 0;
   return (int)grid_for(ceil_div(a.M, kSkU), 256 >> lg, 8192);
 }
 
-bool launch_nt_skinny(const NTArgs& a, hipStream_t st) {
-  if (a.a_bf16 || a.c_bf16 || a.nproj > 0 || a.M == 0) return false;
-  const int K = a.k1 + a.k2;
-  if (a.Nc <= SK_MAXN && K <= SK_KMAX) {
-    if (a.colsum_part) return false;  // (the column sums ride only in the skinny-K form)
+void launch_nt_skinny(const NTArgs& a, hipStream_t st) {
+  const NTSkinny form = nt_skinny_form(a);
+  if (form == SKINNY_N) {
+    const int K = a.k1 + a.k2;
     auto v_ok = [&](int v) {
       return a.k1 % v == 0 && a.lda1 % v == 0 && al(a.a1, 4 * v) &&
              (a.k2 == 0 || (a.k2 % v == 0 && a.lda2 % v == 0 && al(a.a2, 4 * v)));
@@ -300,13 +307,10 @@ bool launch_nt_skinny(const NTArgs& a, hipStream_t st) {
     if (VEC == 4) { GNN_SKN_V(4); } else if (VEC == 2) { GNN_SKN_V(2); } else { GNN_SKN_V(1); }
 #undef GNN_SKN_V
 #undef GNN_SKN
-    return true;
-  }
-  if (a.k2 == 0 && a.k1 <= SK_MAXN && a.Nc <= 64 * 4) {
+  } else if (form == SKINNY_K) {
     const int VEC = skk_vec(a);
     const int lg = lg2ceil((a.Nc + VEC - 1) / VEC);
-    if (lg > 8) return false;
-    const unsigned nb = grid_for(ceil_div(a.M, kSkU), 256 >> lg, 8192);
+    const unsigned nb = (unsigned)nt_skinny_k_blocks(a);
     const int KK = a.k1 <= 1 ? 1 : a.k1 <= 2 ? 2 : a.k1 <= 4 ? 4 : 8;
 #define GNN_SKK(V, KX) nt_skinny_k_kernel<V, KX><<<nb, 256, 0, st>>>(a, lg)
 #define GNN_SKK_V(V) \
@@ -314,9 +318,7 @@ bool launch_nt_skinny(const NTArgs& a, hipStream_t st) {
     if (VEC == 4) { GNN_SKK_V(4); } else if (VEC == 2) { GNN_SKK_V(2); } else { GNN_SKK_V(1); }
 #undef GNN_SKK_V
 #undef GNN_SKK
-    return true;
   }
-  return false;
 }
 
 int tn_skinny_blocks(int64_t M) {

@@ -204,13 +204,9 @@ def gemm_nt(a1, bt, n, a2=None, bias=None, relu=False, dropout_p=0.0, seed=0, pr
     if b_stage == "prep":
         _lib.call("gnn_gemm_nt_prep_b", p, _lib.stream_handle(dev))
         return None
-    if KernelTimer.active:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = KernelTimer.begin()
     _lib.call("gnn_gemm_nt_f32", p, _lib.stream_handle(dev))
-    if KernelTimer.active:
-        e1.record()
+    if e0 is not None:
         k = k1 + k2
         # tag: kind, M, K, N, A element bytes, C element bytes, MFMA products per bf16 term
         # (6 split-bf16, 1 bf16 storage, 0 exact f32, -1 the VALU kernels of the skinny shapes).
@@ -222,8 +218,7 @@ def gemm_nt(a1, bt, n, a2=None, bias=None, relu=False, dropout_p=0.0, seed=0, pr
             prod = 3  # f16 half-pair: 3 products
         if ea == 4 and proj is None and (n <= 8 or (k <= 8 and a2 is None)):
             prod = -1
-        KernelTimer.records.append((("gemm_nt", M, k, n, ea, out.element_size() if out is not None else 0, prod),
-                                    e0, e1, 2 * M * k * n))
+        KernelTimer.end(e0, ("gemm_nt", M, k, n, ea, out.element_size() if out is not None else 0, prod), 2 * M * k * n)
     if colsum:
         from .aggregation import colsum as _colsum
 
@@ -290,10 +285,7 @@ def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gou
         p.sq_partial, p.sq_step = sq[0].data_ptr(), sq[1].data_ptr()
         p.sq_skip_lo, p.sq_skip_hi, p.sq_cap = lo, hi, sq[0].numel()
     ws = torch.empty(max(_tn_ws_bytes(M, nr, k1 + k2, nproj) // 4, 1), dtype=torch.float32, device=dev)
-    if KernelTimer.active:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = KernelTimer.begin()
     if dz_active is not None:
         if dz_active.dtype != torch.uint8 or dz_active.numel() < (M + _lib.ACTIVE_ROWS - 1) // _lib.ACTIVE_ROWS:
             raise ValueError("dz_active: uint8, one per 16 rows of dz")
@@ -308,8 +300,7 @@ def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gou
         # its version counter), so any in-place edit between here and ClipAdam.step — GradScaler's
         # unscale_, a mul_, an all-reduce — bumps it and voids the fold
         grad_sq_produced(dev, (out, n_out, (lo, hi), _sq_blocks(n_out), sq[0], sq[1], out._version))
-    if KernelTimer.active:
-        e1.record()
+    if e0 is not None:
         ea = 2 if bf else (4 if a1 is None else a1.element_size())
         prod = 0 if _math(math) == _lib.MATH_F32 else (1 if ea == 2 else 6)
         if getattr(planes, "fmt", None) == _lib.PLANES_HALF_PAIR or (
@@ -317,8 +308,8 @@ def gemm_tn(nr, a1, a2=None, g=None, dz=None, proj=None, h=None, hscale=1.0, gou
             prod = 3
         if ea == 4 and nr <= 8 and dz is None and h is None and gout is None:
             prod = -1
-        KernelTimer.records.append((("gemm_tn", M, k1 + k2, nr, ea, h.element_size() if h is not None else 4, prod),
-                                    e0, e1, 2 * M * (k1 + k2) * nr))
+        KernelTimer.end(e0, ("gemm_tn", M, k1 + k2, nr, ea, h.element_size() if h is not None else 4, prod),
+                        2 * M * (k1 + k2) * nr)
     o = 0
     dW1 = out[o: o + nr * k1].view(nr, k1)  # contiguous per segment: autograd adopts them, no clone
     o += nr * k1
@@ -352,40 +343,32 @@ def gemm_nt_input(x: torch.Tensor, n: int, **kw):
     return gemm_nt(x, None, n, **kw)
 
 
-def _csc_fold(ctx, dz, u, hscale):
-    """(plan, u) when the 2-layer SAGE backward's one TN (layer 1, half-pair image, dz form, no input
-    gradient) takes the folded CSC sum of u (ABI 26), else None (the caller runs the CSC sum)."""
+def _layer1_dz_tn(ctx, dz, hscale, **extra):
+    """Whether the 2-layer SAGE backward's one TN (layer 1, no input gradient) runs the half-pair dz
+    form over the image of [agg | x], with ``extra`` (gemm_tn keywords) taken inside that kernel."""
     L = ctx.meta[0]
-    if not _TN_CSC or L != 2 or ctx.needs_input_grad[0] or ctx.bimgs[0] is not None:
-        return None
+    if L != 2 or ctx.needs_input_grad[0] or ctx.bimgs[0] is not None:
+        return False
     saved = ctx.saved_tensors
     if saved[L] is not None or getattr(ctx, "image", None) is None or not isinstance(ctx.image[0], HalfPairImage):
-        return None  # layer 1 not on the half-pair image of [agg | x]
-    im = ctx.image[0]
+        return False  # layer 1 not on the half-pair image of [agg | x]
     hs1, Wl0 = saved[1], saved[2 * L - 1]
+    return gemm_tn(Wl0.size(0), None, None, h=hs1, hscale=hscale, planes=ctx.image[0], check_planes=True, dz=dz,
+                   proj=ctx.P, **extra)
+
+
+def _csc_fold(ctx, dz, u, hscale):
+    """(plan, u) when that TN takes the folded CSC sum of u (ABI 26), else None (the caller runs the
+    CSC sum)."""
     csc = (ctx.plan, u)
-    if not gemm_tn(Wl0.size(0), None, None, h=hs1, hscale=hscale, planes=im, check_planes=True, dz=dz, proj=ctx.P,
-                   csc=csc):
-        return None
-    return csc
+    return csc if _TN_CSC and _layer1_dz_tn(ctx, dz, hscale, csc=csc) else None
 
 
 def _tn_active_flags(ctx, dz, hscale):
-    """An empty uint8 flag buffer (one per 16 rows of dz) when the 2-layer SAGE backward's one TN
-    (layer 1, half-pair image, dz form, no input gradient) walks activity flags at this size
-    (gnn_gemm_tn_active_pays: a rule of the row count alone), else None (the dense TN)."""
-    L = ctx.meta[0]
+    """An empty uint8 flag buffer (one per 16 rows of dz) when that TN walks activity flags at this
+    size (gnn_gemm_tn_active_pays: a rule of the row count alone), else None (the dense TN)."""
     N = dz.size(0)
-    if not _TN_ACTIVE or L != 2 or ctx.needs_input_grad[0] or ctx.bimgs[0] is not None:
-        return None
-    saved = ctx.saved_tensors
-    if saved[L] is not None or getattr(ctx, "image", None) is None or not isinstance(ctx.image[0], HalfPairImage):
-        return None  # layer 1 not on the half-pair image of [agg | x]
-    if not _lib.load().gnn_gemm_tn_active_pays(N):
-        return None
-    hs1, Wl0 = saved[1], saved[2 * L - 1]
-    if not gemm_tn(Wl0.size(0), None, None, h=hs1, hscale=hscale, planes=ctx.image[0], check_planes=True, dz=dz,
-                   proj=ctx.P):
+    if not _TN_ACTIVE or not _lib.load().gnn_gemm_tn_active_pays(N) or not _layer1_dz_tn(ctx, dz, hscale):
         return None
     return torch.empty((N + _lib.ACTIVE_ROWS - 1) // _lib.ACTIVE_ROWS, dtype=torch.uint8, device=dz.device)
 
