@@ -25,7 +25,7 @@ __device__ __forceinline__ float leaky(float z, float slope) { return z > 0.0f ?
 
 // Fast-path arithmetic (lane-group kernels): exp as one v_exp_f32 of x*log2(e) (exp(-inf) = 0,
 // relative error ~|x| * 2^-24: the softmax arguments are <= 0 and large |x| carry negligible
-// weight), 1/x as one v_rcp_f32 (1 ulp).  Both well inside the 1e-5 parity bound.
+// weight), 1/x as one v_rcp_f32 (1 ulp).  Held to float64 at scores up to ~300 (test_gpu_gat_numerics).
 __device__ __forceinline__ float fexp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 __device__ __forceinline__ float frcp(float x) { return __builtin_amdgcn_rcpf(x); }
 // 24-bit row offsets (the host routes graphs with N or a row pitch >= 2^24 to the generic kernels)
@@ -213,6 +213,20 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_kernel(GatArgs a) {
       t += a.alpha[(int64_t)k * H + hl] * da;
     }
     t = wave_sum_over_heads(t, H);
+    // t2_h = sum_k alpha_k * (dalpha_k - t): what t's rounding (and sum alpha != 1) left behind.
+    // d e = alpha * (dalpha - t) cancels where the softmax is saturated, and there t's last bit is
+    // the whole result; (dalpha - t) is exact for dalpha near t, so one correction restores it
+    float t2 = 0.0f;
+    for (int32_t idx = lane; idx < npair; idx += 64) {
+      int32_t k = beg + idx / H;
+      int32_t j = a.col[k];
+      const float* xr = a.xh + (int64_t)j * a.ld_xh + (int64_t)hl * C;
+      float da = 0.0f;
+      for (int c = 0; c < C; ++c) da += dO(a, r, hl, c) * xr[c];
+      if (a.ew) da *= a.ew[k];
+      t2 += a.alpha[(int64_t)k * H + hl] * (da - t);
+    }
+    t2 = wave_sum_over_heads(t2, H);
     float sdz = 0.0f;
     for (int32_t idx = lane; idx < npair; idx += 64) {
       int32_t k = beg + idx / H;
@@ -227,7 +241,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_kernel(GatArgs a) {
         if (hl == 0) a.dew[k] = v;
       }
       if (a.ew) da *= a.ew[k];
-      float de = al * (da - t);
+      float de = al * ((da - t) - t2);
       float z = a.a_s[(int64_t)j * H + hl] + adr;
       float dzv = z > 0.0f ? de : de * a.slope;
       a.dz[(int64_t)k * H + hl] = dzv;
@@ -484,6 +498,9 @@ struct Online {
     m = mn;
   }
   __device__ __forceinline__ void merge(float m2, float s2, const VecF<VEC>& acc2) {
+    // no FMA contraction: fma(s, c1, s2 * c2) is not what the exchange partner's fma(s2, c2, s * c1)
+    // rounds to, and the phases of a row would normalise their alpha by sums an ulp apart
+#pragma clang fp contract(off)
     const float mn = fmaxf(m, m2);
     const float c1 = m == -INFINITY ? 0.0f : fexp(m - mn);
     const float c2 = m2 == -INFINITY ? 0.0f : fexp(m2 - mn);
@@ -516,12 +533,12 @@ __device__ __forceinline__ SlotLane slot_lane(const GatGeom& g, int lig, int wid
 
 // The slot pass of one lane: slots beg + ep, += EP, two per trip (both neighbour rows in flight;
 // the lanes of a head share their trip count, so the head_sum exchanges stay converged).  The
-// first trip's weights stay in registers (p0f, p1f with the running max m1 they refer to: most
-// rows end there); later trips park their raw scores in alpha (writer lane) for normalise_alpha.
+// first trip's raw scores stay in registers (e0f, e1f: most rows end there); later trips park
+// theirs in alpha (writer lane) for normalise_alpha.
 template <int VEC, bool XS>
 __device__ __forceinline__ void slot_pass(const GatArgs& a, const SlotLane& sl, int32_t beg, int32_t end, float adr,
-                                          const VecF<VEC>& as_v, bool writer, Online<VEC>& st, float& p0f,
-                                          float& p1f, float& m1) {
+                                          const VecF<VEC>& as_v, bool writer, Online<VEC>& st, float& e0f,
+                                          float& e1f) {
   const int H = a.H;
   const int32_t k0 = beg + sl.ep;
   for (int32_t k = k0; k < end; k += 2 * sl.EP) {
@@ -543,9 +560,8 @@ __device__ __forceinline__ void slot_pass(const GatArgs& a, const SlotLane& sl, 
     float p0, p1;
     st.add2(e0, x0, e1, x1, p0, p1);
     if (k == k0) {
-      p0f = p0;
-      p1f = p1;
-      m1 = st.m;
+      e0f = e0;
+      e1f = e1;
     } else if (writer) {
       a.alpha[roff(k, H) + sl.hs] = e0;
       if (two) a.alpha[roff(k + sl.EP, H) + sl.hs] = e1;
@@ -553,16 +569,17 @@ __device__ __forceinline__ void slot_pass(const GatArgs& a, const SlotLane& sl, 
   }
 }
 
-// alpha = exp(e - m) / denom for the writer lane's slots (rinv = 1 / denom): the first trip as
-// its kept weights rescaled to the final max, later trips from their parked raw scores.
+// alpha = exp(e - m) / denom for the writer lane's slots (rinv = 1 / denom), every slot from its raw
+// score against the row's final max: slots of equal score (duplicate edges) get bit-equal weights
+// whichever trip or phase walked them, and no weight carries a second exp's rounding
+// (exp(e - m1) * exp(m1 - m) was off by tens of ulp at score ranges of 50).
 __device__ __forceinline__ void normalise_alpha(const GatArgs& a, const SlotLane& sl, int32_t beg, int32_t end,
-                                                float p0f, float p1f, float m1, float m, float rinv) {
+                                                float e0f, float e1f, float m, float rinv) {
   const int H = a.H;
   const int32_t k0 = beg + sl.ep;
   if (k0 < end) {
-    const float sc = fexp(m1 - m) * rinv;
-    a.alpha[roff(k0, H) + sl.hs] = p0f * sc;
-    if (k0 + sl.EP < end) a.alpha[roff(k0 + sl.EP, H) + sl.hs] = p1f * sc;
+    a.alpha[roff(k0, H) + sl.hs] = fexp(e0f - m) * rinv;
+    if (k0 + sl.EP < end) a.alpha[roff(k0 + sl.EP, H) + sl.hs] = fexp(e1f - m) * rinv;
   }
 #pragma unroll 1
   for (int32_t k = k0 + 2 * sl.EP; k < end; k += sl.EP) {
@@ -606,8 +623,8 @@ __device__ void gat_fwd_long_row(const GatArgs& a, const GatGeom& g, const GatEp
   const bool writer = sl.ok && sl.fl == sl.hs * sl.L;  // one lane per (head, phase) keeps the raw scores
   Online<VEC> st;
   st.init();
-  float p0f = 0.0f, p1f = 0.0f, m1 = 0.0f;
-  if (sl.ok) slot_pass<VEC, XS>(a, sl, beg, end, adr, as_v, writer, st, p0f, p1f, m1);
+  float e0f = 0.0f, e1f = 0.0f;
+  if (sl.ok) slot_pass<VEC, XS>(a, sl, beg, end, adr, as_v, writer, st, e0f, e1f);
   for (int off = 32; off >= g.FLp; off >>= 1) {
     VecF<VEC> a2;
 #pragma unroll
@@ -664,7 +681,7 @@ __device__ void gat_fwd_long_row(const GatArgs& a, const GatGeom& g, const GatEp
       a.out[r * a.ldo + c] = gat_store_val(ep_, seed, t / (float)H + (a.bias ? a.bias[c] : 0.0f), r, c, Fo);
     }
   }
-  if (writer) normalise_alpha(a, sl, beg, end, p0f, p1f, m1, tot.m, rinv);
+  if (writer) normalise_alpha(a, sl, beg, end, e0f, e1f, tot.m, rinv);
 }
 
 // Forward, short rows (<= T slots): G lanes per row in the slot view, one pass with an online
@@ -728,8 +745,8 @@ __global__ __launch_bounds__(256) void gat_fwd_group_kernel(GatArgs a, GatGeom g
     }
     Online<VEC> st;
     st.init();
-    float p0f = 0.0f, p1f = 0.0f, m1 = 0.0f;
-    if (sl.ok) slot_pass<VEC, XS>(a, sl, beg, end, adr, as_v, writer, st, p0f, p1f, m1);
+    float e0f = 0.0f, e1f = 0.0f;
+    if (sl.ok) slot_pass<VEC, XS>(a, sl, beg, end, adr, as_v, writer, st, e0f, e1f);
     for (int off = G >> 1; off >= g.FLp; off >>= 1) {
       VecF<VEC> a2;
 #pragma unroll
@@ -779,7 +796,7 @@ __global__ __launch_bounds__(256) void gat_fwd_group_kernel(GatArgs a, GatGeom g
         stv<VEC>(a.out + r * a.ldo + sl.c0, o);
       }
     }
-    if (writer) normalise_alpha(a, sl, beg, end, p0f, p1f, m1, st.m, rinv);
+    if (writer) normalise_alpha(a, sl, beg, end, e0f, e1f, st.m, rinv);
   }
 }
 
@@ -824,20 +841,37 @@ __device__ __forceinline__ float bwd_pass1(const GatArgs& a, const SlotLane& sl,
   return t;
 }
 
-// Writer lanes only: dz = leaky'(z) * alpha * (d alpha - t) per slot, returns their sum.
+// Writer lanes only: t2 = sum_k alpha (d alpha - t) over the lane's slots - what t's rounding (and
+// sum alpha != 1) left behind.  d e = alpha (d alpha - t) cancels where the softmax is saturated,
+// and there t's last bit is the whole result; (d alpha - t) is exact for d alpha near t, so this one
+// correction restores it (gat_bwd_rows_kernel does the same).
+__device__ __forceinline__ float bwd_pass1b(const GatArgs& a, const SlotLane& sl, int32_t beg, int32_t end, float t,
+                                            const BwdSlot& q0, const BwdSlot& q1) {
+  const int H = a.H;
+  const int32_t k0 = beg + sl.ep;
+  float t2 = 0.0f;
+  if (k0 < end) t2 += q0.al * (q0.da - t);
+  if (k0 + sl.EP < end) t2 += q1.al * (q1.da - t);
+#pragma unroll 1
+  for (int32_t k = k0 + 2 * sl.EP; k < end; k += sl.EP)
+    t2 += a.alpha[roff(k, H) + sl.hs] * (a.dz[roff(k, H) + sl.hs] - t);  // d alpha parked by this lane
+  return t2;
+}
+
+// Writer lanes only: dz = leaky'(z) * alpha * ((d alpha - t) - t2) per slot, returns their sum.
 __device__ __forceinline__ float bwd_pass2(const GatArgs& a, const SlotLane& sl, int32_t beg, int32_t end, float adr,
-                                           float t, const BwdSlot& q0, const BwdSlot& q1) {
+                                           float t, float t2, const BwdSlot& q0, const BwdSlot& q1) {
   const int H = a.H;
   const int32_t k0 = beg + sl.ep;
   float sdz = 0.0f;
   if (k0 < end) {
-    const float de = q0.al * (q0.da - t);
+    const float de = q0.al * ((q0.da - t) - t2);
     const float v = q0.pos ? de : de * a.slope;
     a.dz[roff(k0, H) + sl.hs] = v;
     sdz += v;
   }
   if (k0 + sl.EP < end) {
-    const float de = q1.al * (q1.da - t);
+    const float de = q1.al * ((q1.da - t) - t2);
     const float v = q1.pos ? de : de * a.slope;
     a.dz[roff(k0 + sl.EP, H) + sl.hs] = v;
     sdz += v;
@@ -846,7 +880,7 @@ __device__ __forceinline__ float bwd_pass2(const GatArgs& a, const SlotLane& sl,
   for (int32_t k = k0 + 2 * sl.EP; k < end; k += sl.EP) {
     const int32_t j = a.col[k];
     float* p = a.dz + roff(k, H) + sl.hs;
-    const float de = a.alpha[roff(k, H) + sl.hs] * (*p - t);
+    const float de = a.alpha[roff(k, H) + sl.hs] * ((*p - t) - t2);
     const float v = a.a_s[roff(j, H) + sl.hs] + adr > 0.0f ? de : de * a.slope;
     *p = v;
     sdz += v;
@@ -913,7 +947,12 @@ __device__ void gat_bwd_long_row(const GatArgs& a, const GatGeom& g, int64_t r, 
   if (lane < g.FLp) sh[wave * 64 + sl.fl] = t;
   __syncthreads();
   t = ((sh[sl.fl] + sh[64 + sl.fl]) + sh[128 + sl.fl]) + sh[192 + sl.fl];
-  float sdz = writer ? bwd_pass2(a, sl, beg, end, adr, t, q0, q1) : 0.0f;
+  float t2 = writer ? bwd_pass1b(a, sl, beg, end, t, q0, q1) : 0.0f;  // (a writer's xor partners are writers)
+  for (int off = 32; off >= g.FLp; off >>= 1) t2 += __shfl_xor(t2, off);
+  if (lane < g.FLp) sh[512 + wave * 64 + sl.fl] = t2;
+  __syncthreads();
+  t2 = ((sh[512 + sl.fl] + sh[576 + sl.fl]) + sh[640 + sl.fl]) + sh[704 + sl.fl];
+  float sdz = writer ? bwd_pass2(a, sl, beg, end, adr, t, t2, q0, q1) : 0.0f;
   for (int off = 32; off >= g.FLp; off >>= 1) sdz += __shfl_xor(sdz, off);
   if (lane < g.FLp) sh[256 + wave * 64 + sl.fl] = sdz;
   __syncthreads();
@@ -923,7 +962,7 @@ __device__ void gat_bwd_long_row(const GatArgs& a, const GatGeom& g, int64_t r, 
 
 template <int VEC>
 __global__ __launch_bounds__(256) void gat_bwd_rows_group_kernel(GatArgs a, GatGeom g, GatLong lg) {
-  __shared__ float sh[512];
+  __shared__ float sh[768];  // the long row's wave partials: t, d a_dst, t2
   if ((int)blockIdx.x < lg.n) {
     gat_bwd_long_row<VEC>(a, g, lg.rows[blockIdx.x], sh);
     return;
@@ -952,7 +991,9 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_group_kernel(GatArgs a, GatG
     BwdSlot q0{0.0f, 0.0f, false}, q1{0.0f, 0.0f, false};
     float t = sl.ok ? bwd_pass1<VEC>(a, sl, beg, end, adr, dO, inv_h, writer, q0, q1) : 0.0f;
     for (int off = G >> 1; off >= g.FLp; off >>= 1) t += __shfl_xor(t, off);
-    float sdz = writer ? bwd_pass2(a, sl, beg, end, adr, t, q0, q1) : 0.0f;
+    float t2 = writer ? bwd_pass1b(a, sl, beg, end, t, q0, q1) : 0.0f;  // (a writer's xor partners are writers)
+    for (int off = G >> 1; off >= g.FLp; off >>= 1) t2 += __shfl_xor(t2, off);
+    float sdz = writer ? bwd_pass2(a, sl, beg, end, adr, t, t2, q0, q1) : 0.0f;
     for (int off = G >> 1; off >= g.FLp; off >>= 1) sdz += __shfl_xor(sdz, off);
     if (own && writer && sl.ep == 0) a.dad[r * H + sl.hs] = sdz;
   }
