@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -425,6 +425,10 @@ SIGNATURES = {
         [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
          c_ptr, c_ptr, c_size, c_ptr],
     ),
+    "gnn_edge_drop_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_edge_drop": (ctypes.c_int, [c_ptr, c_i64, c_i64, ctypes.c_uint64, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_feature_noise_f32": (
+        ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_ptr, c_i64, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

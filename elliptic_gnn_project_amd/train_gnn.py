@@ -716,18 +716,9 @@ def main(cfg: Dict) -> Dict:
         _, _, lv = eval_split(model, data, ei, gmask("val_mask"), **ev)
         vm_dev = gmask("val_mask").to(lv.device)
         yv = (gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y)[vm_dev]
-        Tp = torch.ones(1, device=device, requires_grad=True)
-        lbfgs = torch.optim.LBFGS([Tp], lr=0.1, max_iter=1000)
-        lv = lv[vm_dev].detach()
+        from .robustness import fit_temperature
 
-        def closure():
-            lbfgs.zero_grad()
-            l = F.cross_entropy(lv / Tp, yv.long())
-            l.backward()
-            return l
-
-        lbfgs.step(closure)
-        T = Tp.detach()
+        T = fit_temperature(lv[vm_dev], yv)
         if dist is not None:
             dist.broadcast(T, 0)  # one temperature for every rank
 

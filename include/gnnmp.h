@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 29
+#define GNNMP_ABI_VERSION 30
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -880,6 +880,39 @@ gnn_status gnn_rank_bootstrap(const int32_t* order_a, const int32_t* rank_a, con
                               int64_t num_replicates, int64_t k, double* ap_a, double* ap_b,
                               double* patk_a, double* patk_b, int32_t* status, void* workspace,
                               size_t workspace_bytes, gnn_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K15 seeded input perturbations (ABI 30): drop_edges and maybe_add_noise of
+ *     src/analysis/robustness.py:65-90, from a counter hash with a bit-exact host mirror
+ *     (elliptic_gnn_project_amd/robustness.py) in place of torch.randperm / torch.randn_like   */
+/* ------------------------------------------------------------------------ */
+/*
+ * H(c, key) = fmix32(((uint32)c * 0x9E3779B1 + key_lo) ^ key_hi) (the dropout mask's hash), and
+ * stream_key(seed, s) = splitmix64(seed ^ (s * 0xD1B54A32D192ED03)); streams: 1 edge drop, 2 noise
+ * radius, 3 noise angle.
+ *
+ * gnn_edge_drop: out[2, E - drop_count] = edge_index[2, E] (contiguous int64) without the drop_count
+ * columns e of smallest (H(e, key), e), the kept columns in their original order; key is
+ * stream_key(seed, 1), formed by the caller.  drop_count must lie in [0, num_edges) (INVALID_ARG
+ * otherwise; num_edges = 0 with drop_count = 0 is a no-op); drop_count = 0 launches nothing and leaves
+ * `out` untouched.  The output size is known to the caller: no host synchronisation, capturable.
+ */
+gnn_status gnn_edge_drop_workspace_size(int64_t num_edges, size_t* bytes);
+gnn_status gnn_edge_drop(const int64_t* edge_index, int64_t num_edges, int64_t drop_count, uint64_t key,
+                         int64_t* out, void* workspace, size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * out[row, col] = x[row, col] + noise_std * z(row, col) over [rows, F] f32 (out may be x).  With
+ * P = ceil(F / 2) and c = row * P + col / 2 (one Box-Muller pair per two neighbouring columns):
+ *   u1 = ((H(c, stream_key(key, 2)) >> 8) + 1) * 2^-24,   u2 = (H(c, stream_key(key, 3)) >> 8) * 2^-24,
+ *   r = sqrt(-2 ln u1),   z = r cos(2 pi u2) for even col, r sin(2 pi u2) for odd col;   |z| <= 5.77.
+ * `key` is the call's 64-bit seed; the two stream keys are derived from it on the host.  16-byte
+ * accesses when both bases are 16-byte aligned and both leading dimensions multiples of 4, 8-byte
+ * ones for 8 / 2, else element accesses.  rows = 0 or F = 0 launches nothing.  INVALID_ARG for a
+ * leading dimension below F or rows * P >= 2^32 (the counter is 32 bits wide).
+ */
+gnn_status gnn_feature_noise_f32(const float* x, int64_t ldx, int64_t rows, int64_t F, float noise_std,
+                                 uint64_t key, float* out, int64_t ldo, gnn_stream_t stream);
 
 #ifdef __cplusplus
 }
