@@ -10,7 +10,9 @@ reproducible run to run.
 """
 from __future__ import annotations
 
+import functools
 import os
+from types import SimpleNamespace
 
 import torch
 
@@ -401,6 +403,72 @@ def rowmax_of(g: torch.Tensor):
 _GAT_CE = True  # the CE in the narrow form's launch under fused_ce_target (False: its own launch; A/B, tests)
 
 
+def _gat_fwd_operands(xh, att_src, att_dst, bias, plan: GraphPlan, heads: int, chans: int, concat, slope, act=_lib.ACT_NONE,
+                      dropout_p=0.0, seed=0, seed_ctr=None, edge_w=None, proj=None, z=None):
+    """A forward's operands: the inputs as the kernels take them, the outputs, and the C params ``p``
+    (``bias`` is held beside it until the call: p holds addresses only)."""
+    xh = _as_f32_rows(xh)
+    N, dev = plan.num_nodes, xh.device
+    att_src = att_src.contiguous().float()
+    att_dst = att_dst.contiguous().float()
+    a_src = torch.empty((N, heads), dtype=torch.float32, device=dev)
+    a_dst = torch.empty((N, heads), dtype=torch.float32, device=dev)
+    alpha = torch.empty((max(plan.num_slots, 1), heads), dtype=torch.float32, device=dev)
+    out = torch.empty((N, heads * chans if concat else chans), dtype=torch.float32, device=dev)
+    b = bias.contiguous().float() if bias is not None else None
+    p = _lib.GnnGatFwdParams(
+        heads=heads, chans=chans, concat=int(concat), slope=float(slope), xh=xh.data_ptr(), ld_xh=_ld(xh),
+        att_src=att_src.data_ptr(), att_dst=att_dst.data_ptr(), bias=_lib.ptr(b), act=int(act),
+        dropout_p=float(dropout_p), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, seed_ptr=_lib.ptr(seed_ctr),
+        a_src=a_src.data_ptr(), a_dst=a_dst.data_ptr(), alpha=alpha.data_ptr(), out=out.data_ptr(), ldo=_ld(out),
+        edge_w=_lib.ptr(edge_w), proj=_lib.ptr(proj), nproj=0 if proj is None else proj.size(0), z=_lib.ptr(z),
+        ldz=0 if z is None else _ld(z))
+    return SimpleNamespace(xh=xh, att_src=att_src, att_dst=att_dst, bias=b, a_src=a_src, a_dst=a_dst, alpha=alpha,
+                           out=out, p=p)
+
+
+def _gat_fwd_bytes(S, N, heads, chans, fo, nproj=0):
+    """KernelTimer's bytes of a forward.  Per slot: id 4 + xh row 4HC + alpha 8H (raw score, then
+    normalised); per node: rowptr 4, own xh row 4HC, a_src + a_dst 8H, out 4·fo (+ z 4·nproj)."""
+    return S * (4 + 8 * heads + 4 * heads * chans) + N * (4 + 8 * heads + 4 * heads * chans + 4 * fo + 4 * nproj)
+
+
+@functools.lru_cache(maxsize=256)
+def _gat_bwd_ws_bytes(N, S, heads, chans) -> int:
+    nb = _lib.c_size(0)
+    _lib.call("gnn_gat_bwd_workspace_size", N, S, heads, chans, nb)
+    return int(nb.value)
+
+
+def _gat_bwd_operands(plan: GraphPlan, heads, chans, concat, slope, xh, a_src, a_dst, att_src, att_dst, alpha):
+    """A backward's outputs and workspace, and the C arguments the four backward entries share: ``head``
+    (graph .. alpha; concat None: the store-backward entries, always concat, take none) first, ``grads``
+    (dxh .. d att_dst) after the entry's own gradient inputs, ``tail`` (workspace, stream) last."""
+    N, F, dev = plan.num_nodes, heads * chans, xh.device
+    dxh = torch.empty((N, F), dtype=torch.float32, device=dev)
+    datt_s = torch.empty(F, dtype=torch.float32, device=dev)
+    datt_d = torch.empty(F, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(_gat_bwd_ws_bytes(N, plan.num_slots, heads, chans), 1), dtype=torch.uint8, device=dev)
+    head = (plan.c_graph, heads, chans) + (() if concat is None else (int(concat),)) + (
+        slope, xh.data_ptr(), _ld(xh), a_src.data_ptr(), a_dst.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(),
+        alpha.data_ptr())
+    return SimpleNamespace(dxh=dxh, datt_s=datt_s, datt_d=datt_d, ws=ws, head=head,
+                           grads=(dxh.data_ptr(), _ld(dxh), datt_s.data_ptr(), datt_d.data_ptr()),
+                           tail=(ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)))
+
+
+def _gat_bwd_bytes(S, N, heads, chans, fo):
+    """KernelTimer's bytes of a backward.  Rows pass (dα, de per slot): id 4 + alpha 4H + xh row 4HC +
+    de 4H, dout row 4·fo per node; cols pass (CSC): id+map 8 + alpha/de 8H + dout row 4·fo per slot,
+    dxh 4HC + scores 8H per node."""
+    return S * (12 + 16 * heads + 4 * heads * chans + 4 * fo) + N * (8 + 16 * heads + 4 * heads * chans + 4 * fo)
+
+
+def _gat_post_args(act, dropout_p, seed, seed_ctr, out):
+    """The C arguments of the store's backward: act, dropout and its seed, the stored y."""
+    return (act, dropout_p, seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(seed_ctr), out.data_ptr(), _ld(out))
+
+
 class _GATAttention(torch.autograd.Function):
     """K5/K6 with the scores formed in-kernel (gnn_gat_fwd_fused_f32) and, for GATNet's hidden
     layers, ELU + counter-hash dropout on the store; the backward undoes them in one elementwise
@@ -410,23 +478,9 @@ class _GATAttention(torch.autograd.Function):
     @_custom_fwd
     def forward(ctx, xh, att_src, att_dst, bias, plan: GraphPlan, heads: int, chans: int, concat: bool,
                 slope: float, act: int, dropout_p: float, seed: int, seed_ctr):
-        xh = _as_f32_rows(xh)
-        N = plan.num_nodes
-        dev = xh.device
-        att_src = att_src.contiguous().float()
-        att_dst = att_dst.contiguous().float()
-        stream = _lib.stream_handle(dev)
-        a_src = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        a_dst = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        alpha = torch.empty((max(plan.num_slots, 1), heads), dtype=torch.float32, device=dev)
-        fo = heads * chans if concat else chans
-        out = torch.empty((N, fo), dtype=torch.float32, device=dev)
-        b = bias.contiguous().float() if bias is not None else None
-        p = _lib.GnnGatFwdParams(
-            heads, chans, int(concat), float(slope), xh.data_ptr(), _ld(xh), att_src.data_ptr(), att_dst.data_ptr(),
-            _lib.ptr(b), int(act), float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(seed_ctr),
-            a_src.data_ptr(), a_dst.data_ptr(), alpha.data_ptr(), out.data_ptr(), _ld(out),
-        )
+        f = _gat_fwd_operands(xh, att_src, att_dst, bias, plan, heads, chans, concat, slope, act, dropout_p, seed,
+                              seed_ctr)
+        N, out = plan.num_nodes, f.out
         t0 = KernelTimer.begin()
         ce = None
         if (heads == 1 and chans <= 2 and not concat and act == _lib.ACT_NONE and dropout_p == 0.0 and N > 0
@@ -436,16 +490,13 @@ class _GATAttention(torch.autograd.Function):
             from .train_ops import ce_target, gat_out
 
             tgt = ce_target() if (_GAT_CE and any(ctx.needs_input_grad)) else None
-            ce = gat_out(plan, p, tgt)
+            ce = gat_out(plan, f.p, tgt)
         else:
-            _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, p, stream)
-        S = plan.num_slots
-        # per slot: id 4 + xh row 4HC + alpha 8H (raw score, then normalised); per node: rowptr 4,
-        # own xh row 4HC, a_src + a_dst 8H, out 4·fo
-        KernelTimer.end(t0, ("gat_fwd", heads, chans, fo),
-                        S * (4 + 8 * heads + 4 * heads * chans) + N * (4 + 8 * heads + 4 * heads * chans + 4 * fo))
+            _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, f.p, _lib.stream_handle(out.device))
+        KernelTimer.end(t0, ("gat_fwd", heads, chans, out.size(1)),
+                        _gat_fwd_bytes(plan.num_slots, N, heads, chans, out.size(1)))
         post = act != _lib.ACT_NONE or dropout_p > 0
-        ctx.save_for_backward(xh, att_src, att_dst, a_src, a_dst, alpha, seed_ctr, out if post else None)
+        ctx.save_for_backward(f.xh, f.att_src, f.att_dst, f.a_src, f.a_dst, f.alpha, seed_ctr, out if post else None)
         ctx.meta = (plan, heads, chans, bool(concat), float(slope), bias is not None, int(act), float(dropout_p),
                     int(seed))
         if ce is not None:
@@ -458,43 +509,27 @@ class _GATAttention(torch.autograd.Function):
         xh, att_src, att_dst, a_src, a_dst, alpha, seed_ctr, out = ctx.saved_tensors
         plan, heads, chans, concat, slope, has_bias, act, dropout_p, seed = ctx.meta
         dout = _as_f32_rows(dout)
-        dev = xh.device
-        N = plan.num_nodes
-        F = heads * chans
-        dxh = torch.empty((N, F), dtype=torch.float32, device=dev)
-        datt_s = torch.empty(F, dtype=torch.float32, device=dev)
-        datt_d = torch.empty(F, dtype=torch.float32, device=dev)
-        nb = _lib.c_size(0)
-        _lib.call("gnn_gat_bwd_workspace_size", N, plan.num_slots, heads, chans, nb)
-        ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
+        fused = out is not None and concat  # through dropout(act(.)): d pre formed inside the rows pass
+        b = _gat_bwd_operands(plan, heads, chans, None if fused else concat, slope, xh, a_src, a_dst, att_src, att_dst,
+                              alpha)
         t0 = KernelTimer.begin()
-        if out is not None and concat:  # through dropout(act(.)): d pre formed inside the rows pass
+        if out is not None:
             dpre = torch.empty_like(out)
-            _lib.call("gnn_gat_bwd_act_f32", plan.c_graph, heads, chans, slope, xh.data_ptr(), _ld(xh),
-                      a_src.data_ptr(), a_dst.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(), alpha.data_ptr(),
-                      act, dropout_p, seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(seed_ctr), out.data_ptr(), _ld(out),
-                      dout.data_ptr(), _ld(dout), dpre.data_ptr(), _ld(dpre), dxh.data_ptr(), _ld(dxh),
-                      datt_s.data_ptr(), datt_d.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_handle(dev))
+            post = _gat_post_args(act, dropout_p, seed, seed_ctr, out)
+        if fused:
+            _lib.call("gnn_gat_bwd_act_f32", *b.head, *post, dout.data_ptr(), _ld(dout), dpre.data_ptr(), _ld(dpre),
+                      *b.grads, *b.tail)
             dout = dpre
         else:
             if out is not None:  # through dropout(act(.)) first: d pre
-                dpre = torch.empty_like(out)
-                _lib.call("gnn_gat_act_bwd_f32", N, out.size(1), act, dropout_p, seed & 0xFFFFFFFFFFFFFFFF,
-                          _lib.ptr(seed_ctr), out.data_ptr(), _ld(out), dout.data_ptr(), _ld(dout), dpre.data_ptr(),
-                          _ld(dpre), _lib.stream_handle(dev))
+                _lib.call("gnn_gat_act_bwd_f32", plan.num_nodes, out.size(1), *post, dout.data_ptr(), _ld(dout),
+                          dpre.data_ptr(), _ld(dpre), _lib.stream_handle(xh.device))
                 dout = dpre
-            _lib.call("gnn_gat_bwd_f32", plan.c_graph, heads, chans, int(concat), slope, xh.data_ptr(), _ld(xh),
-                      a_src.data_ptr(), a_dst.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(), alpha.data_ptr(),
-                      dout.data_ptr(), _ld(dout), dxh.data_ptr(), _ld(dxh), datt_s.data_ptr(), datt_d.data_ptr(),
-                      ws.data_ptr(), ws.numel(), _lib.stream_handle(dev))
-        S = plan.num_slots
-        fo = F if concat else chans
-        # rows pass (dα, de per slot): id 4 + alpha 4H + xh row 4HC + de 4H, dout row 4·fo per node;
-        # cols pass (CSC): id+map 8 + alpha/de 8H + dout row 4·fo per slot, dxh 4HC + scores 8H per node
-        KernelTimer.end(t0, ("gat_bwd", heads, chans, fo),
-                        S * (12 + 16 * heads + 4 * heads * chans + 4 * fo) + N * (8 + 16 * heads + 4 * F + 4 * fo))
+            _lib.call("gnn_gat_bwd_f32", *b.head, dout.data_ptr(), _ld(dout), *b.grads, *b.tail)
+        fo = heads * chans if concat else chans
+        KernelTimer.end(t0, ("gat_bwd", heads, chans, fo), _gat_bwd_bytes(plan.num_slots, plan.num_nodes, heads, chans, fo))
         db = colsum_of(dout) if has_bias and ctx.needs_input_grad[3] else None
-        return (dxh, datt_s.view_as(att_src), datt_d.view_as(att_dst), db) + (None,) * 9
+        return (b.dxh, b.datt_s.view_as(att_src), b.datt_d.view_as(att_dst), db) + (None,) * 9
 
 
 class _GATAttentionProj(torch.autograd.Function):
@@ -509,31 +544,15 @@ class _GATAttentionProj(torch.autograd.Function):
     @_custom_fwd
     def forward(ctx, xh, att_src, att_dst, bias, w_out, plan: GraphPlan, heads: int, chans: int, slope: float,
                 act: int, dropout_p: float, seed: int, seed_ctr):
-        xh = _as_f32_rows(xh)
-        N = plan.num_nodes
-        dev = xh.device
-        att_src = att_src.contiguous().float()
-        att_dst = att_dst.contiguous().float()
         w = w_out.contiguous().float()
-        F = heads * chans
-        a_src = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        a_dst = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        alpha = torch.empty((max(plan.num_slots, 1), heads), dtype=torch.float32, device=dev)
-        out = torch.empty((N, F), dtype=torch.float32, device=dev)
-        z = torch.empty((N, w.size(0)), dtype=torch.float32, device=dev)
-        b = bias.contiguous().float() if bias is not None else None
-        p = _lib.GnnGatFwdParams(
-            heads, chans, 1, float(slope), xh.data_ptr(), _ld(xh), att_src.data_ptr(), att_dst.data_ptr(),
-            _lib.ptr(b), int(act), float(dropout_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _lib.ptr(seed_ctr),
-            a_src.data_ptr(), a_dst.data_ptr(), alpha.data_ptr(), out.data_ptr(), _ld(out), None,
-            w.data_ptr(), w.size(0), z.data_ptr(), _ld(z),
-        )
+        N, F = plan.num_nodes, heads * chans
+        z = torch.empty((N, w.size(0)), dtype=torch.float32, device=xh.device)
+        f = _gat_fwd_operands(xh, att_src, att_dst, bias, plan, heads, chans, True, slope, act, dropout_p, seed,
+                              seed_ctr, proj=w, z=z)
         t0 = KernelTimer.begin()
-        _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, p, _lib.stream_handle(dev))
-        S = plan.num_slots
-        KernelTimer.end(t0, ("gat_fwd", heads, chans, F),
-                        S * (4 + 8 * heads + 4 * F) + N * (4 + 8 * heads + 4 * F + 4 * F + 4 * w.size(0)))
-        ctx.save_for_backward(xh, att_src, att_dst, a_src, a_dst, alpha, seed_ctr, out, w)
+        _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, f.p, _lib.stream_handle(z.device))
+        KernelTimer.end(t0, ("gat_fwd", heads, chans, F), _gat_fwd_bytes(plan.num_slots, N, heads, chans, F, w.size(0)))
+        ctx.save_for_backward(f.xh, f.att_src, f.att_dst, f.a_src, f.a_dst, f.alpha, seed_ctr, f.out, w)
         ctx.meta = (plan, heads, chans, float(slope), bias is not None, int(act), float(dropout_p), int(seed))
         return z
 
@@ -545,39 +564,27 @@ class _GATAttentionProj(torch.autograd.Function):
         xh, att_src, att_dst, a_src, a_dst, alpha, seed_ctr, out, w = ctx.saved_tensors
         plan, heads, chans, slope, has_bias, act, dropout_p, seed = ctx.meta
         dz = _as_f32_rows(dz)
-        dev = xh.device
-        N = plan.num_nodes
-        F = heads * chans
+        N, F = plan.num_nodes, heads * chans
         need = ctx.needs_input_grad
         dW = None
         if need[4]:  # dW_out = dzᵀ · h (the skinny TN)
             (dW, _), _, _, _ = gemm_tn(w.size(0), out, g=dz)
-        dxh = torch.empty((N, F), dtype=torch.float32, device=dev)
-        datt_s = torch.empty(F, dtype=torch.float32, device=dev)
-        datt_d = torch.empty(F, dtype=torch.float32, device=dev)
+        b = _gat_bwd_operands(plan, heads, chans, None, slope, xh, a_src, a_dst, att_src, att_dst, alpha)
         dpre = torch.empty_like(out)
-        nb = _lib.c_size(0)
-        _lib.call("gnn_gat_bwd_workspace_size", N, plan.num_slots, heads, chans, nb)
-        ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
         # (ABI 25) max |dxh| per 16-row group, written as dxh is stored: the lin's weight-gradient TN
         # (dW = dxhᵀ · x, the g form over x's half-pair image) takes its block scales from these
         # instead of a pass over dxh (fused.gemm_tn reads the tag)
         rowmax = torch.empty(max((N + _lib.ROWMAX_ROWS - 1) // _lib.ROWMAX_ROWS, 1), dtype=torch.int32,
-                             device=dev) if _GAT_ROWMAX and N > 0 else None
+                             device=xh.device) if _GAT_ROWMAX and N > 0 else None
         t0 = KernelTimer.begin()
-        _lib.call("gnn_gat_bwd_act_proj_f32", plan.c_graph, heads, chans, slope, xh.data_ptr(), _ld(xh),
-                  a_src.data_ptr(), a_dst.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(), alpha.data_ptr(),
-                  act, dropout_p, seed & 0xFFFFFFFFFFFFFFFF, _lib.ptr(seed_ctr), out.data_ptr(), _ld(out),
-                  dz.data_ptr(), _ld(dz), w.data_ptr(), w.size(0), dpre.data_ptr(), _ld(dpre), dxh.data_ptr(),
-                  _ld(dxh), datt_s.data_ptr(), datt_d.data_ptr(), _lib.ptr(rowmax), ws.data_ptr(), ws.numel(),
-                  _lib.stream_handle(dev))
+        _lib.call("gnn_gat_bwd_act_proj_f32", *b.head, *_gat_post_args(act, dropout_p, seed, seed_ctr, out),
+                  dz.data_ptr(), _ld(dz), w.data_ptr(), w.size(0), dpre.data_ptr(), _ld(dpre), *b.grads,
+                  _lib.ptr(rowmax), *b.tail)
         if rowmax is not None:
-            tag_rowmax(dxh, rowmax)
-        S = plan.num_slots
-        KernelTimer.end(t0, ("gat_bwd", heads, chans, F),
-                        S * (12 + 16 * heads + 4 * F + 4 * F) + N * (8 + 16 * heads + 4 * F + 4 * F))
+            tag_rowmax(b.dxh, rowmax)
+        KernelTimer.end(t0, ("gat_bwd", heads, chans, F), _gat_bwd_bytes(plan.num_slots, N, heads, chans, F))
         db = colsum(dpre) if has_bias and need[3] else None
-        return (dxh, datt_s.view_as(att_src), datt_d.view_as(att_dst), db, dW) + (None,) * 8
+        return (b.dxh, b.datt_s.view_as(att_src), b.datt_d.view_as(att_dst), db, dW) + (None,) * 8
 
 
 def gat_attention_proj(xh: torch.Tensor, att_src: torch.Tensor, att_dst: torch.Tensor, bias: torch.Tensor | None,
@@ -610,27 +617,12 @@ class _GATAttentionMasked(torch.autograd.Function):
     @_custom_fwd
     def forward(ctx, xh, att_src, att_dst, bias, w_slot, plan: GraphPlan, heads: int, chans: int, concat: bool,
                 slope: float):
-        xh = _as_f32_rows(xh)
-        N = plan.num_nodes
-        dev = xh.device
-        att_src = att_src.contiguous().float()
-        att_dst = att_dst.contiguous().float()
         w_slot = w_slot.contiguous().float()
-        a_src = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        a_dst = torch.empty((N, heads), dtype=torch.float32, device=dev)
-        alpha = torch.empty((max(plan.num_slots, 1), heads), dtype=torch.float32, device=dev)
-        fo = heads * chans if concat else chans
-        out = torch.empty((N, fo), dtype=torch.float32, device=dev)
-        b = bias.contiguous().float() if bias is not None else None
-        p = _lib.GnnGatFwdParams(
-            heads, chans, int(concat), float(slope), xh.data_ptr(), _ld(xh), att_src.data_ptr(), att_dst.data_ptr(),
-            _lib.ptr(b), _lib.ACT_NONE, 0.0, 0, None, a_src.data_ptr(), a_dst.data_ptr(), alpha.data_ptr(),
-            out.data_ptr(), _ld(out), w_slot.data_ptr(),
-        )
-        _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, p, _lib.stream_handle(dev))
-        ctx.save_for_backward(xh, att_src, att_dst, a_src, a_dst, alpha, w_slot)
+        f = _gat_fwd_operands(xh, att_src, att_dst, bias, plan, heads, chans, concat, slope, edge_w=w_slot)
+        _lib.call("gnn_gat_fwd_fused_f32", plan.c_graph, f.p, _lib.stream_handle(f.out.device))
+        ctx.save_for_backward(f.xh, f.att_src, f.att_dst, f.a_src, f.a_dst, f.alpha, w_slot)
         ctx.meta = (plan, heads, chans, bool(concat), float(slope), bias is not None)
-        return out
+        return f.out
 
     @staticmethod
     @_custom_bwd
@@ -638,22 +630,12 @@ class _GATAttentionMasked(torch.autograd.Function):
         xh, att_src, att_dst, a_src, a_dst, alpha, w_slot = ctx.saved_tensors
         plan, heads, chans, concat, slope, has_bias = ctx.meta
         dout = _as_f32_rows(dout)
-        dev = xh.device
-        N = plan.num_nodes
-        F = heads * chans
-        dxh = torch.empty((N, F), dtype=torch.float32, device=dev)
-        datt_s = torch.empty(F, dtype=torch.float32, device=dev)
-        datt_d = torch.empty(F, dtype=torch.float32, device=dev)
+        b = _gat_bwd_operands(plan, heads, chans, concat, slope, xh, a_src, a_dst, att_src, att_dst, alpha)
         dw = torch.empty_like(w_slot)
-        nb = _lib.c_size(0)
-        _lib.call("gnn_gat_bwd_workspace_size", N, plan.num_slots, heads, chans, nb)
-        ws = torch.empty(max(int(nb.value), 1), dtype=torch.uint8, device=dev)
-        _lib.call("gnn_gat_bwd_ew_f32", plan.c_graph, heads, chans, int(concat), slope, xh.data_ptr(), _ld(xh),
-                  a_src.data_ptr(), a_dst.data_ptr(), att_src.data_ptr(), att_dst.data_ptr(), alpha.data_ptr(),
-                  dout.data_ptr(), _ld(dout), dxh.data_ptr(), _ld(dxh), datt_s.data_ptr(), datt_d.data_ptr(),
-                  w_slot.data_ptr(), dw.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_handle(dev))
+        _lib.call("gnn_gat_bwd_ew_f32", *b.head, dout.data_ptr(), _ld(dout), *b.grads, w_slot.data_ptr(), dw.data_ptr(),
+                  *b.tail)
         db = colsum_of(dout) if has_bias and ctx.needs_input_grad[3] else None
-        return (dxh, datt_s.view_as(att_src), datt_d.view_as(att_dst), db, dw) + (None,) * 5
+        return (b.dxh, b.datt_s.view_as(att_src), b.datt_d.view_as(att_dst), db, dw) + (None,) * 5
 
 
 def masked_gat_attention(xh: torch.Tensor, att_src: torch.Tensor, att_dst: torch.Tensor, bias: torch.Tensor | None,

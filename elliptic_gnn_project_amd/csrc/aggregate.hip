@@ -1342,14 +1342,6 @@ AggLab agg_lab() {
 constexpr AggLab agg_lab() { return {}; }
 #endif
 
-// The run-time vector width as a compile-time constant: f(std::integral_constant<int, vec>).
-template <class Fn>
-void with_vec(int vec, Fn&& f) {
-  if (vec == 4) f(std::integral_constant<int, 4>{});
-  else if (vec == 2) f(std::integral_constant<int, 2>{});
-  else f(std::integral_constant<int, 1>{});
-}
-
 // lanes per row of the lane-group gather
 int flat_lps(int nchunk) { return nchunk <= 8 ? 8 : nchunk <= 16 ? 16 : nchunk <= 32 ? 32 : 64; }
 

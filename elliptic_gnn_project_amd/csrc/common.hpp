@@ -43,6 +43,14 @@ inline gnn_status hip_check(hipError_t e, const char* fn) {
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// The run-time vector width as a compile-time constant (host): f(std::integral_constant<int, vec>).
+template <class Fn>
+void with_vec(int vec, Fn&& f) {
+  if (vec == 4) f(std::integral_constant<int, 4>{});
+  else if (vec == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 1>{});
+}
+
 // Bump allocator over a caller-provided workspace (256-B aligned carves).
 struct WorkspaceCarver {
   char* base;

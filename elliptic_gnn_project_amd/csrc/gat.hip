@@ -1509,7 +1509,56 @@ GatLong long_rows(const gnn_graph* g) {
 
 constexpr int64_t kColsBlocks = 2048;  // cols-pass grid cap = number of d att partials
 
-bool pow2_heads(int H) { return H >= 1 && H <= 64 && (H & (H - 1)) == 0; }
+// Which kernels a call runs, decided once and launching nothing: the lane-group kernels with their
+// vector width, geometry, long rows and grids, or (group false) the generic one-wave-per-row ones.
+struct GatRoute {
+  bool group;
+  int vec;
+  GatGeom gg;
+  GatLong lg;
+  unsigned rows_blocks, cols_blocks;  // forward / rows pass (one block more per long row), cols pass
+};
+
+// ops: the operands the group kernels access VEC floats at a time; extra: the caller's own clauses
+GatRoute gat_route(const gnn_graph* g, int H, int C, int concat, int64_t ld_xh,
+                   std::initializer_list<std::pair<const void*, int64_t>> ops, bool extra) {
+  GatRoute r{};
+  r.vec = 1;
+  r.group = extra && idx24_ok(g, ld_xh, H) && gat_geom(H, C, concat, ops, &r.gg, &r.vec);
+  if (!r.group) return r;
+  r.lg = long_rows(g);
+  r.rows_blocks = group_blocks(g->num_nodes, r.gg.G, (int64_t)1 << 20) + (unsigned)r.lg.n;
+  r.cols_blocks = group_blocks(g->num_nodes, r.gg.G, kColsBlocks);
+  return r;
+}
+
+// The refusals several entry points share: GNN_OK when the arguments pass.
+gnn_status check_heads(const char* fn, int H) {
+  if (H >= 1 && H <= 64 && (H & (H - 1)) == 0) return GNN_OK;
+  return fail(GNN_ERR_UNSUPPORTED, fn, "heads must be a power of two <= 64");
+}
+gnn_status check_act_dropout(const char* fn, int act, float p) {
+  if (act != GNN_ACT_NONE && act != GNN_ACT_ELU) return fail(GNN_ERR_INVALID_ARG, fn, "unknown act");
+  return p >= 0.0f && p < 1.0f ? GNN_OK : fail(GNN_ERR_INVALID_ARG, fn, "dropout_p not in [0, 1)");
+}
+gnn_status check_dropout_index(const char* fn, float p, int64_t rows, int64_t width) {
+  if (!(p > 0.0f) || rows * width < ((int64_t)1 << 32)) return GNN_OK;
+  return fail(GNN_ERR_UNSUPPORTED, fn, "dropout element index (rows x width) must be < 2^32");
+}
+
+gnn_status launched(const char* fn) { return hip_check(hipGetLastError(), fn); }
+
+// The GatArgs fields every entry point sets (bwd: the plan's CSC side too).
+GatArgs gat_args(const gnn_graph* g, bool bwd, int H, int C, int concat, float slope, const float* xh, int64_t ld_xh,
+                 const float* a_src, const float* a_dst, const float* att_src, const float* att_dst) {
+  GatArgs a{};
+  a.rowptr = g->rowptr; a.col = g->col;
+  if (bwd) { a.colptr = g->colptr; a.row = g->row; a.csc2csr = g->csc2csr; }
+  a.order = csr_order(g);
+  a.N = g->num_nodes; a.H = H; a.C = C; a.concat = concat; a.slope = slope;
+  a.xh = xh; a.ld_xh = ld_xh; a.a_s = a_src; a.a_d = a_dst; a.att_s = att_src; a.att_d = att_dst;
+  return a;
+}
 
 unsigned row_blocks(int64_t N) {
   int64_t b = ceil_div(N, 4);
@@ -1522,7 +1571,7 @@ void carve_bwd(C& c, int64_t N, int64_t S, int H, int C_, float** dz, float** da
   auto p0 = c.template take<float>((size_t)(S > 0 ? S : 1) * H);
   auto p1 = c.template take<float>((size_t)(N > 0 ? N : 1) * H);
   auto p2 = c.template take<float>((size_t)(N > 0 ? N : 1) * H);
-  auto p3 = c.template take<float>((size_t)2048 * 2 * H * C_);  // max(kAttBlocks, kColsBlocks)
+  auto p3 = c.template take<float>((size_t)std::max<int64_t>(kAttBlocks, kColsBlocks) * 2 * H * C_);  // d att partials
   if (dz) { *dz = (float*)p0; *dad = (float*)p1; *das = (float*)p2; *part = (float*)p3; }
 }
 
@@ -1531,6 +1580,186 @@ struct SizerAdapter {
   template <typename T>
   T* take(size_t n) { s.take<T>(n); return nullptr; }
 };
+
+// Both forwards.  XS: the scores formed in-kernel from the attention vectors and written out, the
+// store's activation / dropout / projection (gnn_gat_fwd_fused_f32); else a_src / a_dst are inputs
+// and the store is plain (gnn_gat_fwd_f32: p holds no act, dropout, edge_w or proj).
+gnn_status gat_fwd(const char* fn, const gnn_graph* g, const gnn_gat_fwd_params* p, bool xs, gnn_stream_t stream) {
+  const int32_t H = p->heads, C = p->chans, concat = p->concat;
+  const int64_t F = (int64_t)H * C, Fo = concat ? F : C;
+  if (gnn_status s = check_heads(fn, H)) return s;
+  if (C < 1 || p->ld_xh < F || p->ldo < Fo) return fail(GNN_ERR_INVALID_ARG, fn, "bad sizes");
+  if (gnn_status s = check_act_dropout(fn, p->act, p->dropout_p)) return s;
+  if (gnn_status s = check_dropout_index(fn, p->dropout_p, g->num_nodes, Fo)) return s;
+  if (g->num_nodes == 0) return GNN_OK;
+  if (!p->xh || (xs && (!p->att_src || !p->att_dst)) || !p->a_src || !p->a_dst || !p->alpha || !p->out || !g->rowptr ||
+      !g->col)
+    return fail(GNN_ERR_INVALID_ARG, fn, "null");
+  if (p->nproj < 0 || p->nproj > 4 || (p->nproj > 0 && (!concat || !p->proj || !p->z || p->ldz < p->nproj ||
+                                                          (reinterpret_cast<uintptr_t>(p->proj) & 15))))
+    return fail(GNN_ERR_INVALID_ARG, fn, "proj: concat, nproj <= 4, proj (16-byte aligned) and z");
+  GatArgs a = gat_args(g, false, H, C, concat, p->slope, p->xh, p->ld_xh, p->a_src, p->a_dst, p->att_src, p->att_dst);
+  a.bias = p->bias; a.alpha = p->alpha; a.out = p->out; a.ldo = p->ldo; a.ew = p->edge_w;
+  GatEpi ep{};
+  if (xs) {
+    ep = make_epi(p->act, p->dropout_p, p->seed, p->seed_ptr);
+    ep.as_out = p->a_src; ep.ad_out = p->a_dst;
+    ep.proj = p->proj; ep.nproj = p->nproj; ep.z = p->z; ep.ldz = p->ldz;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  // the group kernels take no edge_w, and a projection only at F % 4 == 0, nproj <= 2, F <= 256
+  const GatRoute r =
+      gat_route(g, H, C, concat, p->ld_xh, {{p->xh, p->ld_xh}, {p->out, p->ldo}, {p->att_src, 0}, {p->att_dst, 0}},
+                !p->edge_w && (p->nproj == 0 || (F % 4 == 0 && p->nproj <= 2 && F <= 256)));
+  if (r.group) {
+    const auto launch = [&](auto v, auto x) {
+      gat_fwd_group_kernel<decltype(v)::value, decltype(x)::value><<<r.rows_blocks, 256, 0, st>>>(a, r.gg, r.lg, ep);
+    };
+    if (!xs) with_vec(r.vec, [&](auto v) { launch(v, std::false_type{}); });
+    else with_vec(r.vec, [&](auto v) { launch(v, std::true_type{}); });
+    return launched(fn);
+  }
+  // generic geometry: scores pass, one wave per row, then the activation / dropout pass
+  if (xs) {
+    gat_scores_kernel<<<(unsigned)ceil_div(a.N * H, 256), 256, 0, st>>>(a.N, H, C, p->xh, p->ld_xh, p->att_src,
+                                                                        p->att_dst, p->a_src, p->a_dst);
+    if (gnn_status s = launched(fn)) return s;
+  }
+  gat_fwd_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
+  if (gnn_status s = launched(fn)) return s;
+  if (ep.act != GNN_ACT_NONE || ep.dropout) {
+    gat_act_fwd_kernel<<<elem_blocks(a.N * Fo), 256, 0, st>>>(a.N, (int32_t)Fo, p->out, p->ldo, ep);
+    if (gnn_status s = launched(fn)) return s;
+  }
+  if (ep.nproj > 0) {
+    gat_proj_rows_kernel<<<elem_blocks(a.N), 256, 0, st>>>(a.N, H * C, p->out, p->ldo, ep.proj, ep.nproj, ep.z, ep.ldz);
+    if (gnn_status s = launched(fn)) return s;
+  }
+  return GNN_OK;
+}
+
+// max |x| over each GNN_ROWMAX_ROWS-row group of x [N, F] (float bits, one wave per group): the
+// generic kernels' dxh_rowmax (the group kernels form it as they store dxh)
+__global__ __launch_bounds__(256) void rowmax_group_kernel(const float* __restrict__ x, int64_t ld, int64_t N, int32_t F,
+                                                          uint32_t* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t grp = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+  const int64_t r0 = grp * GNN_ROWMAX_ROWS;
+  if (r0 >= N) return;
+  const int64_t n = min<int64_t>(GNN_ROWMAX_ROWS, N - r0) * F;
+  float m = 0.0f;
+  for (int64_t e = lane; e < n; e += 64) m = fmaxf(m, fabsf(x[(r0 + e / F) * ld + e % F]));
+  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+  if (lane == 0) out[grp] = __float_as_uint(m);
+}
+
+// The backward of a hidden layer's store, dropout(act(.)), riding in the attention backward: d pre is
+// formed from dy (or, dz set, from dy = dz · proj) and the stored y, and written to dpre.  ep is the
+// forward's store (what the generic kernels' own pass, gat_act_bwd_kernel, takes); keep = 1 - p.
+struct GatPost {
+  GatEpi ep;
+  float keep;
+  const float* y; int64_t ld_y;
+  float* dpre; int64_t ld_dpre;
+  const float* dz; int64_t ld_dz; const float* proj; int32_t nproj;
+  uint32_t* dxh_rowmax;  // optional: max |dxh| per GNN_ROWMAX_ROWS-row group
+};
+
+GatPost make_post(int act, float dropout_p, uint64_t seed, const uint64_t* seed_ptr, const float* y, int64_t ld_y,
+                  float* dpre, int64_t ld_dpre, const float* dz = nullptr, int64_t ld_dz = 0, const float* proj = nullptr,
+                  int32_t nproj = 0, uint32_t* dxh_rowmax = nullptr) {
+  return GatPost{make_epi(act, dropout_p, seed, seed_ptr), (float)(1.0 - (double)dropout_p), y, ld_y, dpre, ld_dpre,
+                 dz, ld_dz, proj, nproj, dxh_rowmax};
+}
+
+// the group rows pass with the post fused: its operands in the kernel's arguments
+void apply_post(const GatPost& p, GatArgs* a) {
+  a->y = p.y; a->ld_y = p.ld_y; a->dpre = p.dpre; a->ld_dpre = p.ld_dpre;
+  a->pe_act = p.ep.act; a->pe_drop = p.ep.dropout; a->pe_thresh = p.ep.keep_thresh; a->pe_scale = p.ep.drop_scale;
+  a->pe_keep = p.keep; a->pe_seed = p.ep.seed; a->pe_seed_ptr = p.ep.seed_ptr;
+  a->pdz = p.dz; a->ld_pdz = p.ld_dz; a->pproj = p.proj; a->pnproj = p.nproj;
+  a->dxh_rowmax = p.dxh_rowmax;
+}
+
+gnn_status gat_bwd_impl(const char* fn, const gnn_graph* g, int32_t H, int32_t C, int32_t concat, float slope,
+                        const float* xh, int64_t ld_xh, const float* a_src, const float* a_dst, const float* att_src,
+                        const float* att_dst, const float* alpha, const float* dout, int64_t ld_dout, float* dxh,
+                        int64_t ld_dxh, float* d_att_src, float* d_att_dst, const float* edge_w, float* d_edge_w,
+                        void* workspace, size_t workspace_bytes, gnn_stream_t stream, const GatPost* post = nullptr) {
+  if (!g) return fail(GNN_ERR_INVALID_ARG, fn, "null graph");
+  if (gnn_status s = check_heads(fn, H)) return s;
+  const int64_t F = (int64_t)H * C;
+  const bool dzf = post && post->dz;  // dy given as dz · proj (dout = dz, ld_dout its pitch)
+  if (C < 1 || ld_xh < F || ld_dxh < F || (dzf ? ld_dout < post->nproj : ld_dout < (concat ? F : C)))
+    return fail(GNN_ERR_INVALID_ARG, fn, "bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  if (g->num_nodes == 0) {
+    if (gnn_status s = hip_check(hipMemsetAsync(d_att_src, 0, F * sizeof(float), st), fn)) return s;
+    return hip_check(hipMemsetAsync(d_att_dst, 0, F * sizeof(float), st), fn);
+  }
+  if (!xh || !a_src || !a_dst || !att_src || !att_dst || !alpha || !dout || !dxh || !d_att_src || !d_att_dst ||
+      !g->colptr || !g->row || !g->csc2csr)
+    return fail(GNN_ERR_INVALID_ARG, fn, "null");
+  WorkspaceCarver c(workspace, workspace_bytes);
+  GatArgs a = gat_args(g, true, H, C, concat, slope, xh, ld_xh, a_src, a_dst, att_src, att_dst);
+  float* part = nullptr;
+  carve_bwd(c, g->num_nodes, g->num_slots, H, C, &a.dz, &a.dad, &a.das, &part);
+  if (!c.ok) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
+  a.alpha = const_cast<float*>(alpha); a.dout = dout; a.ld_dout = ld_dout; a.dxh = dxh; a.ld_dxh = ld_dxh;
+  a.ew = edge_w; a.dew = d_edge_w;
+  // the group kernels take no edge_w, and the dz form only at F % 4 == 0
+  const GatRoute r = gat_route(g, H, C, concat, ld_xh,
+                               {{xh, ld_xh}, {dzf ? nullptr : dout, dzf ? 0 : ld_dout}, {dxh, ld_dxh}, {att_src, 0},
+                                {att_dst, 0}, {post ? post->y : nullptr, post ? post->ld_y : 0},
+                                {post ? post->dpre : nullptr, post ? post->ld_dpre : 0}},
+                               !edge_w && (!dzf || F % 4 == 0));
+  if (r.group) {
+    GatArgs ar = a;  // rows pass: dy in, d pre formed and written (the post rides in it); cols pass reads d pre
+    if (post) {
+      apply_post(*post, &ar);
+      a.dout = post->dpre; a.ld_dout = post->ld_dpre; a.dxh_rowmax = post->dxh_rowmax;
+    }
+    gnn_status s = GNN_OK;
+    with_vec(r.vec, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      gat_bwd_rows_group_kernel<V><<<r.rows_blocks, 256, 0, st>>>(ar, r.gg, r.lg);
+      if ((s = launched(fn)) != GNN_OK) return;
+      gat_bwd_cols_group_kernel<V><<<r.cols_blocks, 256, 0, st>>>(a, r.gg, part);
+      s = launched(fn);
+    });
+    if (s != GNN_OK) return s;
+    gat_att_reduce_kernel<<<(unsigned)(2 * F), 256, 0, st>>>((int)F, (int)r.cols_blocks, part, d_att_src, d_att_dst);
+    return launched(fn);
+  }
+  if (dzf) {  // generic geometry, dz form: dy = dz · proj into dpre first (the act pass below is in place)
+    gat_dz_proj_kernel<<<elem_blocks(a.N * F), 256, 0, st>>>(a.N, (int32_t)F, post->dz, post->ld_dz, post->proj,
+                                                             post->nproj, post->dpre, post->ld_dpre);
+    if (gnn_status s = launched(fn)) return s;
+    dout = post->dpre; ld_dout = post->ld_dpre;
+  }
+  if (post) {  // generic geometry: the store's backward as its own pass first
+    gat_act_bwd_kernel<<<elem_blocks(a.N * F), 256, 0, st>>>(a.N, (int32_t)F, post->ep, post->keep, post->y,
+                                                            post->ld_y, dout, ld_dout, post->dpre, post->ld_dpre);
+    if (gnn_status s = launched(fn)) return s;
+    a.dout = post->dpre; a.ld_dout = post->ld_dpre;
+  }
+  gat_bwd_rows_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
+  if (gnn_status s = launched(fn)) return s;
+  gat_bwd_cols_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
+  if (gnn_status s = launched(fn)) return s;
+  if (post && post->dxh_rowmax) {  // the generic kernels: the row-group maxima in a pass of their own
+    rowmax_group_kernel<<<(unsigned)ceil_div(ceil_div(a.N, GNN_ROWMAX_ROWS), 4), 256, 0, st>>>(
+        dxh, ld_dxh, a.N, (int32_t)F, post->dxh_rowmax);
+    if (gnn_status s = launched(fn)) return s;
+  }
+  int64_t nblk = a.N < kAttBlocks ? a.N : kAttBlocks;
+  int64_t rpb = ceil_div(a.N, nblk);
+  nblk = ceil_div(a.N, rpb);
+  gat_att_partial_kernel<<<(unsigned)nblk, 256, 0, st>>>(a, rpb, part);
+  if (gnn_status s = launched(fn)) return s;
+  gat_att_final_kernel<<<(unsigned)ceil_div(F, 256), 256, 0, st>>>((int)F, (int)nblk, part, d_att_src, d_att_dst);
+  return launched(fn);
+}
 
 }  // namespace
 }  // namespace gnnmp
@@ -1547,8 +1776,7 @@ extern "C" gnn_status gnn_gat_scores_f32(int64_t N, int32_t H, int32_t C, const 
   hipStream_t st = (hipStream_t)stream;
   gat_scores_kernel<<<(unsigned)ceil_div(N * H, 256), 256, 0, st>>>(N, H, C, xh, ld_xh, att_src, att_dst,
                                                                     a_src, a_dst);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  return launched(__func__);
 }
 
 extern "C" gnn_status gnn_gat_fwd_f32(const gnn_graph* g, int32_t H, int32_t C, int32_t concat, float slope,
@@ -1556,92 +1784,16 @@ extern "C" gnn_status gnn_gat_fwd_f32(const gnn_graph* g, int32_t H, int32_t C, 
                                       const float* bias, float* alpha, float* out, int64_t ldo,
                                       gnn_stream_t stream) {
   if (!g) return fail(GNN_ERR_INVALID_ARG, __func__, "null graph");
-  if (!pow2_heads(H)) return fail(GNN_ERR_UNSUPPORTED, __func__, "heads must be a power of two <= 64");
-  if (C < 1 || ld_xh < (int64_t)H * C || ldo < (concat ? (int64_t)H * C : C))
-    return fail(GNN_ERR_INVALID_ARG, __func__, "bad sizes");
-  if (g->num_nodes == 0) return GNN_OK;
-  if (!xh || !a_src || !a_dst || !alpha || !out || !g->rowptr || !g->col)
-    return fail(GNN_ERR_INVALID_ARG, __func__, "null");
-  GatArgs a{};
-  a.rowptr = g->rowptr; a.col = g->col; a.N = g->num_nodes;
-  a.order = csr_order(g);
-  a.H = H; a.C = C; a.concat = concat; a.slope = slope;
-  a.xh = xh; a.ld_xh = ld_xh; a.a_s = a_src; a.a_d = a_dst; a.bias = bias;
-  a.alpha = alpha; a.out = out; a.ldo = ldo;
-  hipStream_t st = (hipStream_t)stream;
-  GatGeom gg;
-  int vec = 1;
-  if (idx24_ok(g, ld_xh, H) && gat_geom(H, C, concat, {{xh, ld_xh}, {out, ldo}}, &gg, &vec)) {
-    const GatLong lg = long_rows(g);
-    const unsigned nb = group_blocks(a.N, gg.G, (int64_t)1 << 20) + (unsigned)lg.n;
-    const GatEpi ep{};
-    if (vec == 4) gat_fwd_group_kernel<4, false><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-    else if (vec == 2) gat_fwd_group_kernel<2, false><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-    else gat_fwd_group_kernel<1, false><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-  } else {
-    gat_fwd_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
-  }
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  gnn_gat_fwd_params p{};
+  p.heads = H; p.chans = C; p.concat = concat; p.slope = slope; p.xh = xh; p.ld_xh = ld_xh; p.bias = bias;
+  p.a_src = const_cast<float*>(a_src); p.a_dst = const_cast<float*>(a_dst);  // read only without XS
+  p.alpha = alpha; p.out = out; p.ldo = ldo;
+  return gat_fwd(__func__, g, &p, false, stream);
 }
 
 extern "C" gnn_status gnn_gat_fwd_fused_f32(const gnn_graph* g, const gnn_gat_fwd_params* p, gnn_stream_t stream) {
   if (!g || !p) return fail(GNN_ERR_INVALID_ARG, __func__, "null graph or params");
-  const int32_t H = p->heads, C = p->chans, concat = p->concat;
-  if (!pow2_heads(H)) return fail(GNN_ERR_UNSUPPORTED, __func__, "heads must be a power of two <= 64");
-  if (C < 1 || p->ld_xh < (int64_t)H * C || p->ldo < (concat ? (int64_t)H * C : C))
-    return fail(GNN_ERR_INVALID_ARG, __func__, "bad sizes");
-  if (p->act != GNN_ACT_NONE && p->act != GNN_ACT_ELU) return fail(GNN_ERR_INVALID_ARG, __func__, "unknown act");
-  if (!(p->dropout_p >= 0.0f && p->dropout_p < 1.0f)) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout_p not in [0, 1)");
-  if (p->dropout_p > 0.0f && (int64_t)g->num_nodes * (concat ? (int64_t)H * C : (int64_t)C) >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
-  if (g->num_nodes == 0) return GNN_OK;
-  if (!p->xh || !p->att_src || !p->att_dst || !p->a_src || !p->a_dst || !p->alpha || !p->out || !g->rowptr || !g->col)
-    return fail(GNN_ERR_INVALID_ARG, __func__, "null");
-  GatArgs a{};
-  a.rowptr = g->rowptr; a.col = g->col; a.N = g->num_nodes;
-  a.order = csr_order(g);
-  a.H = H; a.C = C; a.concat = concat; a.slope = p->slope;
-  a.xh = p->xh; a.ld_xh = p->ld_xh; a.a_s = p->a_src; a.a_d = p->a_dst; a.bias = p->bias;
-  a.att_s = p->att_src; a.att_d = p->att_dst;
-  a.alpha = p->alpha; a.out = p->out; a.ldo = p->ldo;
-  a.ew = p->edge_w;
-  GatEpi ep = make_epi(p->act, p->dropout_p, p->seed, p->seed_ptr);
-  ep.as_out = p->a_src;
-  ep.ad_out = p->a_dst;
-  if (p->nproj < 0 || p->nproj > 4 || (p->nproj > 0 && (!concat || !p->proj || !p->z || p->ldz < p->nproj ||
-                                                          (reinterpret_cast<uintptr_t>(p->proj) & 15))))
-    return fail(GNN_ERR_INVALID_ARG, __func__, "proj: concat, nproj <= 4, proj (16-byte aligned) and z");
-  ep.proj = p->proj; ep.nproj = p->nproj; ep.z = p->z; ep.ldz = p->ldz;
-  hipStream_t st = (hipStream_t)stream;
-  GatGeom gg;
-  int vec = 1;
-  if (!p->edge_w && idx24_ok(g, p->ld_xh, H) && (p->nproj == 0 || ((H * C) % 4 == 0 && p->nproj <= 2 && H * C <= 256)) &&
-      gat_geom(H, C, concat, {{p->xh, p->ld_xh}, {p->out, p->ldo}, {p->att_src, 0}, {p->att_dst, 0}}, &gg, &vec)) {
-    const GatLong lg = long_rows(g);
-    const unsigned nb = group_blocks(a.N, gg.G, (int64_t)1 << 20) + (unsigned)lg.n;
-    if (vec == 4) gat_fwd_group_kernel<4, true><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-    else if (vec == 2) gat_fwd_group_kernel<2, true><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-    else gat_fwd_group_kernel<1, true><<<nb, 256, 0, st>>>(a, gg, lg, ep);
-    GNN_LAUNCH_CHECK();
-    return GNN_OK;
-  }
-  // generic geometry: scores pass, one wave per row, then the activation / dropout pass
-  gat_scores_kernel<<<(unsigned)ceil_div(a.N * H, 256), 256, 0, st>>>(a.N, H, C, p->xh, p->ld_xh, p->att_src,
-                                                                      p->att_dst, p->a_src, p->a_dst);
-  GNN_LAUNCH_CHECK();
-  gat_fwd_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
-  GNN_LAUNCH_CHECK();
-  if (ep.act != GNN_ACT_NONE || ep.dropout) {
-    const int32_t Fo = concat ? H * C : C;
-    gat_act_fwd_kernel<<<elem_blocks(a.N * Fo), 256, 0, st>>>(a.N, Fo, p->out, p->ldo, ep);
-    GNN_LAUNCH_CHECK();
-  }
-  if (ep.nproj > 0) {
-    gat_proj_rows_kernel<<<elem_blocks(a.N), 256, 0, st>>>(a.N, H * C, p->out, p->ldo, ep.proj, ep.nproj, ep.z, ep.ldz);
-    GNN_LAUNCH_CHECK();
-  }
-  return GNN_OK;
+  return gat_fwd(__func__, g, p, true, stream);
 }
 
 extern "C" gnn_status gnn_gat_act_bwd_f32(int64_t N, int64_t F, gnn_act act, float dropout_p, uint64_t seed,
@@ -1649,37 +1801,16 @@ extern "C" gnn_status gnn_gat_act_bwd_f32(int64_t N, int64_t F, gnn_act act, flo
                                           int64_t lddy, float* dpre, int64_t ld_dpre, gnn_stream_t stream) {
   if (N < 0 || F < 1 || F > INT32_MAX || ldy < F || lddy < F || ld_dpre < F)
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad sizes");
-  if (act != GNN_ACT_NONE && act != GNN_ACT_ELU) return fail(GNN_ERR_INVALID_ARG, __func__, "unknown act");
-  if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout_p not in [0, 1)");
-  if (dropout_p > 0.0f && N * F >= ((int64_t)1 << 32)) return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
+  if (gnn_status s = check_act_dropout(__func__, act, dropout_p)) return s;
+  if (gnn_status s = check_dropout_index(__func__, dropout_p, N, F)) return s;
   if (N == 0) return GNN_OK;
   if (!y || !dy || !dpre) return fail(GNN_ERR_INVALID_ARG, __func__, "null");
   const GatEpi ep = make_epi(act, dropout_p, seed, seed_ptr);
   const float keep_p = (float)(1.0 - (double)dropout_p);
   gat_act_bwd_kernel<<<elem_blocks(N * F), 256, 0, (hipStream_t)stream>>>(N, (int32_t)F, ep, keep_p, y, ldy, dy,
                                                                          lddy, dpre, ld_dpre);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  return launched(__func__);
 }
-
-namespace gnnmp {
-namespace {
-// max |x| over each GNN_ROWMAX_ROWS-row group of x [N, F] (float bits, one wave per group): the
-// generic kernels' dxh_rowmax (the group kernels form it as they store dxh)
-__global__ __launch_bounds__(256) void rowmax_group_kernel(const float* __restrict__ x, int64_t ld, int64_t N, int32_t F,
-                                                          uint32_t* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t grp = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
-  const int64_t r0 = grp * GNN_ROWMAX_ROWS;
-  if (r0 >= N) return;
-  const int64_t n = min<int64_t>(GNN_ROWMAX_ROWS, N - r0) * F;
-  float m = 0.0f;
-  for (int64_t e = lane; e < n; e += 64) m = fmaxf(m, fabsf(x[(r0 + e / F) * ld + e % F]));
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if (lane == 0) out[grp] = __float_as_uint(m);
-}
-}  // namespace
-}  // namespace gnnmp
 
 extern "C" gnn_status gnn_gat_bwd_workspace_size(int64_t N, int64_t S, int32_t H, int32_t C, size_t* bytes) {
   if (!bytes || N < 0 || S < 0 || H < 1 || C < 1) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
@@ -1688,115 +1819,6 @@ extern "C" gnn_status gnn_gat_bwd_workspace_size(int64_t N, int64_t S, int32_t H
   *bytes = a.s.used + 256;
   return GNN_OK;
 }
-
-namespace gnnmp {
-namespace {
-gnn_status gat_bwd_impl(const char* fn, const gnn_graph* g, int32_t H, int32_t C, int32_t concat, float slope,
-                        const float* xh, int64_t ld_xh, const float* a_src, const float* a_dst, const float* att_src,
-                        const float* att_dst, const float* alpha, const float* dout, int64_t ld_dout, float* dxh,
-                        int64_t ld_dxh, float* d_att_src, float* d_att_dst, const float* edge_w, float* d_edge_w,
-                        void* workspace, size_t workspace_bytes, gnn_stream_t stream, const GatArgs* post = nullptr) {
-  if (!g) return fail(GNN_ERR_INVALID_ARG, fn, "null graph");
-  if (!pow2_heads(H)) return fail(GNN_ERR_UNSUPPORTED, fn, "heads must be a power of two <= 64");
-  const int64_t F = (int64_t)H * C;
-  const bool dzf = post && post->pdz;  // dy given as dz · proj (dout = dz, ld_dout its pitch)
-  if (C < 1 || ld_xh < F || ld_dxh < F || (dzf ? ld_dout < post->pnproj : ld_dout < (concat ? F : C)))
-    return fail(GNN_ERR_INVALID_ARG, fn, "bad sizes");
-  hipStream_t st = (hipStream_t)stream;
-  if (g->num_nodes == 0) {
-    GNN_HIP_TRY(hipMemsetAsync(d_att_src, 0, F * sizeof(float), st));
-    GNN_HIP_TRY(hipMemsetAsync(d_att_dst, 0, F * sizeof(float), st));
-    return GNN_OK;
-  }
-  if (!xh || !a_src || !a_dst || !att_src || !att_dst || !alpha || !dout || !dxh || !d_att_src || !d_att_dst ||
-      !g->colptr || !g->row || !g->csc2csr)
-    return fail(GNN_ERR_INVALID_ARG, fn, "null");
-  WorkspaceCarver c(workspace, workspace_bytes);
-  GatArgs a{};
-  float* part = nullptr;
-  carve_bwd(c, g->num_nodes, g->num_slots, H, C, &a.dz, &a.dad, &a.das, &part);
-  if (!c.ok) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
-  a.rowptr = g->rowptr; a.col = g->col; a.colptr = g->colptr; a.row = g->row; a.csc2csr = g->csc2csr;
-  a.order = csr_order(g);
-  a.N = g->num_nodes; a.H = H; a.C = C; a.concat = concat; a.slope = slope;
-  a.xh = xh; a.ld_xh = ld_xh; a.a_s = a_src; a.a_d = a_dst;
-  a.att_s = att_src; a.att_d = att_dst; a.alpha = const_cast<float*>(alpha);
-  a.dout = dout; a.ld_dout = ld_dout; a.dxh = dxh; a.ld_dxh = ld_dxh;
-  a.ew = edge_w; a.dew = d_edge_w;
-  GatGeom gg;
-  int vec = 1;
-  const bool fuse = post != nullptr;  // the store's backward rides in the rows pass
-  const int64_t F_ = (int64_t)H * C;
-  if (!edge_w && idx24_ok(g, ld_xh, H) && (!dzf || F % 4 == 0) &&
-      gat_geom(H, C, concat, {{xh, ld_xh}, {dzf ? nullptr : dout, dzf ? 0 : ld_dout}, {dxh, ld_dxh}, {att_src, 0}, {att_dst, 0},
-                              {fuse ? post->y : nullptr, fuse ? post->ld_y : 0},
-                              {fuse ? post->dpre : nullptr, fuse ? post->ld_dpre : 0}}, &gg, &vec)) {
-    const GatLong lg = long_rows(g);
-    const unsigned nbr = group_blocks(a.N, gg.G, (int64_t)1 << 20) + (unsigned)lg.n;
-    const unsigned nbc = group_blocks(a.N, gg.G, kColsBlocks);
-    GatArgs ar = a;  // rows pass: dy in, d pre formed and written; cols pass reads d pre
-    if (fuse) {
-      ar.y = post->y; ar.ld_y = post->ld_y; ar.dpre = post->dpre; ar.ld_dpre = post->ld_dpre;
-      ar.pe_act = post->pe_act; ar.pe_drop = post->pe_drop; ar.pe_thresh = post->pe_thresh;
-      ar.pe_scale = post->pe_scale; ar.pe_keep = post->pe_keep; ar.pe_seed = post->pe_seed;
-      ar.pe_seed_ptr = post->pe_seed_ptr;
-      ar.pdz = post->pdz; ar.ld_pdz = post->ld_pdz; ar.pproj = post->pproj; ar.pnproj = post->pnproj;
-      a.dout = post->dpre; a.ld_dout = post->ld_dpre;
-      ar.dxh_rowmax = a.dxh_rowmax = post->dxh_rowmax;
-    }
-    switch (vec) {
-#define GNN_GAT_BWD(V)                                                            \
-  case V:                                                                         \
-    gat_bwd_rows_group_kernel<V><<<nbr, 256, 0, st>>>(ar, gg, lg);                \
-    GNN_LAUNCH_CHECK();                                                           \
-    gat_bwd_cols_group_kernel<V><<<nbc, 256, 0, st>>>(a, gg, part);               \
-    break;
-      GNN_GAT_BWD(4)
-      GNN_GAT_BWD(2)
-      default: GNN_GAT_BWD(1)
-#undef GNN_GAT_BWD
-    }
-    GNN_LAUNCH_CHECK();
-    gat_att_reduce_kernel<<<(unsigned)(2 * F), 256, 0, st>>>((int)F, (int)nbc, part, d_att_src, d_att_dst);
-    GNN_LAUNCH_CHECK();
-    return GNN_OK;
-  }
-  if (fuse && dzf) {  // generic geometry, dz form: dy = dz · proj into dpre first (the act pass below is in place)
-    gat_dz_proj_kernel<<<elem_blocks(a.N * F_), 256, 0, st>>>(a.N, (int32_t)F_, post->pdz, post->ld_pdz, post->pproj,
-                                                              post->pnproj, post->dpre, post->ld_dpre);
-    GNN_LAUNCH_CHECK();
-    dout = post->dpre;
-    ld_dout = post->ld_dpre;
-  }
-  if (fuse) {  // generic geometry: the store's backward as its own pass first
-    GatEpi ep{};
-    ep.act = post->pe_act; ep.dropout = post->pe_drop; ep.keep_thresh = post->pe_thresh; ep.drop_scale = post->pe_scale;
-    ep.seed = post->pe_seed; ep.seed_ptr = post->pe_seed_ptr;
-    gat_act_bwd_kernel<<<elem_blocks(a.N * F_), 256, 0, st>>>(a.N, (int32_t)F_, ep, post->pe_keep, post->y, post->ld_y,
-                                                             dout, ld_dout, post->dpre, post->ld_dpre);
-    GNN_LAUNCH_CHECK();
-    a.dout = post->dpre; a.ld_dout = post->ld_dpre;
-  }
-  gat_bwd_rows_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
-  GNN_LAUNCH_CHECK();
-  gat_bwd_cols_kernel<<<row_blocks(a.N), 256, 0, st>>>(a);
-  GNN_LAUNCH_CHECK();
-  if (post && post->dxh_rowmax) {  // the generic kernels: the row-group maxima in a pass of their own
-    rowmax_group_kernel<<<(unsigned)ceil_div(ceil_div(a.N, GNN_ROWMAX_ROWS), 4), 256, 0, st>>>(
-        dxh, ld_dxh, a.N, (int32_t)F_, post->dxh_rowmax);
-    GNN_LAUNCH_CHECK();
-  }
-  int64_t nblk = a.N < kAttBlocks ? a.N : kAttBlocks;
-  int64_t rpb = ceil_div(a.N, nblk);
-  nblk = ceil_div(a.N, rpb);
-  gat_att_partial_kernel<<<(unsigned)nblk, 256, 0, st>>>(a, rpb, part);
-  GNN_LAUNCH_CHECK();
-  gat_att_final_kernel<<<(unsigned)ceil_div(F, 256), 256, 0, st>>>((int)F, (int)nblk, part, d_att_src, d_att_dst);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
-}
-}  // namespace
-}  // namespace gnnmp
 
 extern "C" gnn_status gnn_gat_bwd_f32(const gnn_graph* g, int32_t H, int32_t C, int32_t concat, float slope,
                                       const float* xh, int64_t ld_xh, const float* a_src, const float* a_dst,
@@ -1817,17 +1839,11 @@ extern "C" gnn_status gnn_gat_bwd_act_f32(const gnn_graph* g, int32_t H, int32_t
                                           int64_t ld_dxh, float* d_att_src, float* d_att_dst, void* workspace,
                                           size_t workspace_bytes, gnn_stream_t stream) {
   const int64_t F = (int64_t)H * C;
-  if (act != GNN_ACT_NONE && act != GNN_ACT_ELU) return fail(GNN_ERR_INVALID_ARG, __func__, "unknown act");
-  if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout_p not in [0, 1)");
+  if (gnn_status s = check_act_dropout(__func__, act, dropout_p)) return s;
   if (!g || (g->num_nodes > 0 && (!y || !dpre)) || ld_y < F || ld_dpre < F)
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad y / dpre");
-  if (dropout_p > 0.0f && g->num_nodes * F >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
-  GatArgs post{};
-  const GatEpi ep = make_epi(act, dropout_p, seed, seed_ptr);
-  post.y = y; post.ld_y = ld_y; post.dpre = dpre; post.ld_dpre = ld_dpre;
-  post.pe_act = ep.act; post.pe_drop = ep.dropout; post.pe_thresh = ep.keep_thresh; post.pe_scale = ep.drop_scale;
-  post.pe_keep = (float)(1.0 - (double)dropout_p); post.pe_seed = seed; post.pe_seed_ptr = seed_ptr;
+  if (gnn_status s = check_dropout_index(__func__, dropout_p, g->num_nodes, F)) return s;
+  const GatPost post = make_post(act, dropout_p, seed, seed_ptr, y, ld_y, dpre, ld_dpre);
   return gat_bwd_impl(__func__, g, H, C, 1, slope, xh, ld_xh, a_src, a_dst, att_src, att_dst, alpha, dy, ld_dy, dxh,
                       ld_dxh, d_att_src, d_att_dst, nullptr, nullptr, workspace, workspace_bytes, stream, &post);
 }
@@ -1841,20 +1857,12 @@ extern "C" gnn_status gnn_gat_bwd_act_proj_f32(const gnn_graph* g, int32_t H, in
                                                float* d_att_src, float* d_att_dst, uint32_t* dxh_rowmax, void* workspace,
                                                size_t workspace_bytes, gnn_stream_t stream) {
   const int64_t F = (int64_t)H * C;
-  if (act != GNN_ACT_NONE && act != GNN_ACT_ELU) return fail(GNN_ERR_INVALID_ARG, __func__, "unknown act");
-  if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(GNN_ERR_INVALID_ARG, __func__, "dropout_p not in [0, 1)");
+  if (gnn_status s = check_act_dropout(__func__, act, dropout_p)) return s;
   if (!g || (g->num_nodes > 0 && (!y || !dpre || !dz || !proj)) || ld_y < F || ld_dpre < F || nproj < 1 || nproj > 4 ||
       ld_dz < nproj || (reinterpret_cast<uintptr_t>(proj) & 15))
     return fail(GNN_ERR_INVALID_ARG, __func__, "bad y / dpre / dz / proj");
-  if (dropout_p > 0.0f && g->num_nodes * F >= ((int64_t)1 << 32))
-    return fail(GNN_ERR_UNSUPPORTED, __func__, "dropout element index (rows x width) must be < 2^32");
-  GatArgs post{};
-  const GatEpi ep = make_epi(act, dropout_p, seed, seed_ptr);
-  post.y = y; post.ld_y = ld_y; post.dpre = dpre; post.ld_dpre = ld_dpre;
-  post.pe_act = ep.act; post.pe_drop = ep.dropout; post.pe_thresh = ep.keep_thresh; post.pe_scale = ep.drop_scale;
-  post.pe_keep = (float)(1.0 - (double)dropout_p); post.pe_seed = seed; post.pe_seed_ptr = seed_ptr;
-  post.pdz = dz; post.ld_pdz = ld_dz; post.pproj = proj; post.pnproj = nproj;
-  post.dxh_rowmax = dxh_rowmax;
+  if (gnn_status s = check_dropout_index(__func__, dropout_p, g->num_nodes, F)) return s;
+  const GatPost post = make_post(act, dropout_p, seed, seed_ptr, y, ld_y, dpre, ld_dpre, dz, ld_dz, proj, nproj, dxh_rowmax);
   return gat_bwd_impl(__func__, g, H, C, 1, slope, xh, ld_xh, a_src, a_dst, att_src, att_dst, alpha, dz, ld_dz, dxh,
                       ld_dxh, d_att_src, d_att_dst, nullptr, nullptr, workspace, workspace_bytes, stream, &post);
 }

@@ -94,6 +94,49 @@ def test_gat_producer_rowmax_is_exact(device):
     assert torch.equal(seen["rm"], _rowmax(seen["g"]))
 
 
+@pytest.mark.parametrize("graph", ["small", "hub"])
+def test_gat_generic_route_rowmax_is_exact(device, graph):
+    """The generic one-wave-per-row backward forms dxh_rowmax in a pass of its own (gat.hip
+    rowmax_group_kernel).  xh [n, 256] carved 4 bytes past a 16-byte boundary lowers the vector width
+    to 1, 256 slots > 64, so gat_route answers generic; n = 37 (two full 16-row groups and one of 5)
+    and n = 300 (a last group of 12, one degree-3000 row).  The tag equals the per-16-row max |dxh|."""
+    from dispatch_operands import Carved
+    from test_gpu_parity import GRAPHS, rand_graph
+
+    from elliptic_gnn_project_amd import _lib, aggregation
+
+    seen = {}
+    real = aggregation.tag_rowmax
+
+    def spy(g, rm):
+        seen["g"], seen["rm"] = g, rm
+        real(g, rm)
+
+    H, C, n = 4, 64, GRAPHS[graph]["n"]
+    F = H * C
+    ei = rand_graph(**GRAPHS[graph]).to(device)
+    g_ = torch.Generator().manual_seed(11)
+    cx = Carved(n, F, ("flat", 1), device, data=torch.randn(n, F, generator=g_))
+    xh = cx.view.detach().requires_grad_(True)
+    assert xh.data_ptr() % 8 == 4 and xh.stride(0) == F
+    att_s, att_d = (torch.randn(1, H, C, generator=g_).to(device) for _ in range(2))
+    bias = torch.randn(F, generator=g_).to(device)
+    w_out = (torch.randn(2, F, generator=g_) * 0.1).to(device).requires_grad_(True)
+    dz = torch.randn(n, 2, generator=g_).to(device)
+    aggregation.tag_rowmax = spy
+    try:
+        z = aggregation.gat_attention_proj(xh, att_s, att_d, bias, w_out, ei, H, C, 0.2, _lib.ACT_ELU, 0.5,
+                                           0x1234_5678_9ABC, None)
+        z.backward(dz)
+        torch.cuda.synchronize()
+    finally:
+        aggregation.tag_rowmax = real
+    assert "g" in seen and seen["g"].shape == (n, F)
+    assert seen["rm"].numel() == (n + R - 1) // R
+    assert torch.equal(seen["rm"], _rowmax(seen["g"]))
+    assert torch.equal(xh.grad, seen["g"]) and bool(seen["g"].abs().amax() > 0)
+
+
 @pytest.mark.parametrize("layers,heads,hidden", [(2, 4, 64), (3, 4, 64)])
 def test_gat_step_rowmax_bit_identical(device, layers, heads, hidden):
     """The GAT train step with the producer's maxima == the step with the TN's own scan, bit for bit
