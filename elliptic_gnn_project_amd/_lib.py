@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -214,6 +214,27 @@ class GnnCeSpec(ctypes.Structure):
         ("y", c_ptr), ("mask", c_ptr), ("class_w", c_ptr), ("row_w", c_ptr),
         ("inv_denom", ctypes.c_float), ("focal", c_i32), ("focal_gamma", ctypes.c_float),
         ("reserved", c_i32 * 5),
+    ]
+
+
+EXPLAIN_STATUS_BLOCK = 1  # GNN_EXPLAIN_STATUS_BLOCK (ABI 31)
+
+
+class GnnExplainStepParams(ctypes.Structure):
+    """gnn_explain_step_params (ABI 31): one mask's fused GNNExplainer step (K16)."""
+    _fields_ = [
+        ("n", c_i64), ("F", c_i64),
+        ("mask", c_ptr), ("ld_mask", c_i64),
+        ("grad", c_ptr),
+        ("dh", c_ptr), ("ld_dh", c_i64),
+        ("x", c_ptr), ("ld_x", c_i64),
+        ("h", c_ptr), ("ld_h", c_i64),
+        ("exp_avg", c_ptr), ("exp_avg_sq", c_ptr), ("ld_state", c_i64),
+        ("hard", c_ptr), ("hard_out", c_ptr), ("ld_hard", c_i64),
+        ("block_of", c_ptr), ("num_blocks", c_i32), ("t", c_i32),
+        ("size_scale", c_ptr), ("ent_scale", c_ptr),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+        ("status", c_ptr),
     ]
 
 
@@ -429,6 +450,7 @@ SIGNATURES = {
     "gnn_edge_drop": (ctypes.c_int, [c_ptr, c_i64, c_i64, ctypes.c_uint64, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_feature_noise_f32": (
         ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_ptr, c_i64, c_ptr]),
+    "gnn_explain_mask_step_f32": (ctypes.c_int, [ctypes.POINTER(GnnExplainStepParams), c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

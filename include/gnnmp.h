@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 30
+#define GNNMP_ABI_VERSION 31
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -913,6 +913,70 @@ gnn_status gnn_edge_drop(const int64_t* edge_index, int64_t num_edges, int64_t d
  */
 gnn_status gnn_feature_noise_f32(const float* x, int64_t ldx, int64_t rows, int64_t F, float noise_std,
                                  uint64_t key, float* out, int64_t ldo, gnn_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K16 fused GNNExplainer mask step (ABI 31): the per-epoch update of one mask of PyG 2.5.3
+ *     GNNExplainer (src/analysis/explain.py:593-672 drives it) in one launch: the hard-entry
+ *     size and entropy regularisers' gradient, torch.optim.Adam's step and, for the node-feature
+ *     mask, the sigmoid gate's backward and the next forward's h = x * sigmoid(mask)           */
+/* ------------------------------------------------------------------------ */
+#define GNN_EXPLAIN_STATUS_BLOCK 1 /* a block id outside [0, num_blocks): that row / element was skipped */
+
+/*
+ * One mask of logits.  Plain form (x == NULL; the edge mask): mask, grad, exp_avg, exp_avg_sq,
+ * hard / hard_out and block_of are [n] arrays (F and every leading dimension are ignored) and `grad`
+ * is the autograd gradient wrt the logits.  Gate form (x != NULL; the node-feature mask): [n, F]
+ * matrices with leading dimensions (elements), block_of[n] per row, and the gradient is
+ * dh * x * s * (1 - s) with s = sigmoid(mask) and dh the gradient wrt h = x * s.
+ *
+ *   g = grad + hard * s (1 - s) (size_scale[b] + ent_scale[b] * (-log(s + EPS) - s / (s + EPS)
+ *                                               + log(1 - s + EPS) + (1 - s) / (1 - s + EPS)))
+ * with b = block_of[.], EPS = 1e-15 and 1 - s evaluated as sigmoid(-mask); then torch.optim.Adam's
+ * step t (>= 1) on mask / exp_avg / exp_avg_sq: exp_avg = beta1 exp_avg + (1 - beta1) g,
+ * exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g^2, mask -= lr / (1 - beta1^t) * exp_avg /
+ * (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps).  hard == NULL is epoch 0: no regulariser
+ * (size_scale / ent_scale may be NULL) and hard_out = (grad != 0) is written.  The gate form then
+ * writes h = x * sigmoid(mask) from the updated logits when h != NULL.  t == 0 (gate form only)
+ * updates nothing and only writes h.
+ *
+ * A row / element whose block id lies outside [0, num_blocks) is left untouched and sets
+ * GNN_EXPLAIN_STATUS_BLOCK in *status (a plain store of the bit; the caller zeroes and reads the
+ * word).  16-byte accesses when every f32 base is 16-byte aligned and every leading dimension a
+ * multiple of 4 (the byte masks: 4-byte aligned), 8-byte ones for 8 / 2, else element accesses; the
+ * last partial group of a row goes element by element.  Elementwise, no atomics: bitwise
+ * reproducible.  n = 0 or (gate form) F = 0 launches nothing.  INVALID_ARG before any launch: a
+ * leading dimension below F, t < 0, t == 0 in the plain form or without h, num_blocks < 1, n or F
+ * negative, or a missing mask / grad (dh, x) / moment / block_of / status / hard_out (epoch 0) /
+ * scale (later epochs) pointer.
+ */
+typedef struct {
+  int64_t n;                /* elements (plain form) or rows (gate form) */
+  int64_t F;                /* gate form: columns */
+  float* mask;              /* logits, updated in place */
+  int64_t ld_mask;
+  const float* grad;        /* plain form: d loss / d mask */
+  const float* dh;          /* gate form: d loss / d h */
+  int64_t ld_dh;
+  const float* x;           /* gate form: the gated features */
+  int64_t ld_x;
+  float* h;                 /* gate form, optional: x * sigmoid(updated mask) */
+  int64_t ld_h;
+  float* exp_avg;           /* Adam moments, shaped as mask, sharing ld_state */
+  float* exp_avg_sq;
+  int64_t ld_state;
+  const uint8_t* hard;      /* hard mask (non-zero = hard); NULL: epoch 0 */
+  uint8_t* hard_out;        /* epoch 0: receives grad != 0 */
+  int64_t ld_hard;          /* of hard and hard_out */
+  const int32_t* block_of;  /* [n] block of each element / row */
+  int32_t num_blocks;       /* B >= 1 */
+  int32_t t;                /* Adam step count of this call, 1-based; 0: only write h */
+  const float* size_scale;  /* [B] coefficient of sum s over the block's hard entries */
+  const float* ent_scale;   /* [B] coefficient of sum ent(s) over the block's hard entries */
+  double lr, beta1, beta2, eps; /* torch.optim.Adam's; 1 - beta and the bias corrections are formed in double */
+  int32_t* status;          /* device status word */
+} gnn_explain_step_params;
+
+gnn_status gnn_explain_mask_step_f32(const gnn_explain_step_params* p, gnn_stream_t stream);
 
 #ifdef __cplusplus
 }
