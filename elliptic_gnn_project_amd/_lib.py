@@ -15,7 +15,7 @@ import torch  # noqa: F401  (loads the HIP runtime before libgnnmp)
 
 PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ["GNNMP_LIB"]) if os.environ.get("GNNMP_LIB") else PKG_DIR / "libgnnmp.so"  # (GNNMP_LIB: A/B builds)
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 # gnn_dtype
 DTYPE_F32 = 0
@@ -218,6 +218,14 @@ class GnnCeSpec(ctypes.Structure):
 
 
 EXPLAIN_STATUS_BLOCK = 1  # GNN_EXPLAIN_STATUS_BLOCK (ABI 31)
+
+
+# K17 (ABI 32)
+FIT_THREADS = 1024  # GNN_FIT_THREADS
+(FIT_STATUS_LABEL, FIT_STATUS_NAN, FIT_STATUS_EMPTY, FIT_STATUS_FLAT, FIT_STATUS_CLAMP_LOW, FIT_STATUS_CLAMP_HIGH,
+ FIT_STATUS_MAXIT) = 1, 2, 4, 8, 16, 32, 64
+CURVE_OUTPUTS = 8  # GNN_CURVE_OUTPUTS
+CALIB_MAX_BINS = 32  # GNN_CALIB_MAX_BINS
 
 
 class GnnExplainStepParams(ctypes.Structure):
@@ -451,6 +459,18 @@ SIGNATURES = {
     "gnn_feature_noise_f32": (
         ctypes.c_int, [c_ptr, c_i64, c_i64, c_i64, ctypes.c_float, ctypes.c_uint64, c_ptr, c_i64, c_ptr]),
     "gnn_explain_mask_step_f32": (ctypes.c_int, [ctypes.POINTER(GnnExplainStepParams), c_ptr]),
+    "gnn_temperature_fit_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_temperature_fit": (
+        ctypes.c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_rank_curve_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_rank_curve": (
+        ctypes.c_int,
+        [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_threshold_calibration_workspace_size": (ctypes.c_int, [c_i64, c_i32, ctypes.POINTER(c_size)]),
+    "gnn_threshold_calibration": (
+        ctypes.c_int,
+        [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_i32, c_ptr, c_ptr, c_ptr,
+         c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

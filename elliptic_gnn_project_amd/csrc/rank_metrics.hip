@@ -22,6 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "common.hpp"
+#include "rank_scan.hpp"
 
 namespace gnnmp {
 namespace {
@@ -34,8 +35,6 @@ constexpr int kBootTB = 1024;                   // threads of a bootstrap workgr
 constexpr int kBootLdsN = GNN_RANK_BOOT_LDS_MAX_N;
 constexpr int kBootLdsWords = kBootLdsN + kBootLdsN / 32;  // one pad word per 32 (chunked walks hit all banks)
 static_assert((size_t)kBootLdsWords * 4 + 4096 <= 160 * 1024, "the LDS histogram must fit one CU's 160 KiB");
-
-enum : uint8_t { kGroupEnd = 1, kSegStart = 2, kGroupStart = 4 };
 
 // ------------------------------------------------------------------------ scan states
 struct Cnt {  // segmented counts: tp/fp since the last segment start, gtp since the last group start
@@ -68,45 +67,6 @@ struct PartOp {
   }
 };
 static_assert(sizeof(Cnt) == 20 && sizeof(Part) == 24, "scan states move between lanes as 32-bit words");
-
-template <typename T>
-__device__ __forceinline__ T shfl_up_words(const T& v, int d) {
-  constexpr int W = sizeof(T) / 4;
-  int w[W];
-  T r;
-  __builtin_memcpy(w, &v, sizeof(T));
-#pragma unroll
-  for (int i = 0; i < W; ++i) w[i] = __shfl_up(w[i], d, kWave);
-  __builtin_memcpy(&r, w, sizeof(T));
-  return r;
-}
-
-// Exclusive prefix of v over the block's threads (thread order) and the block total, for any
-// associative op: a shuffle scan inside each wave, then the wave totals combined serially in
-// wave order — one fixed tree.  Every thread of the block calls it.
-template <int NW, typename T, typename Op>
-__device__ __forceinline__ void block_scan(const T& v, Op op, const T& ident, T* wave_tot, T* excl, T* total) {
-  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
-  T inc = v;
-#pragma unroll
-  for (int d = 1; d < kWave; d <<= 1) {
-    T o = shfl_up_words(inc, d);
-    if (lane >= d) inc = op(o, inc);
-  }
-  T ex = shfl_up_words(inc, 1);
-  if (lane == 0) ex = ident;
-  __syncthreads();  // wave_tot may still be read from an earlier scan
-  if (lane == kWave - 1) wave_tot[wid] = inc;
-  __syncthreads();
-  T pre = ident, tot = ident;
-  for (int w = 0; w < NW; ++w) {
-    const T t = wave_tot[w];
-    if (w < wid) pre = op(pre, t);
-    tot = op(tot, t);
-  }
-  *excl = op(pre, ex);
-  *total = tot;
-}
 
 // ------------------------------------------------------------------------ rank plan
 // Orderable image of a score, inverted: ascending key = descending score.  -0.0 counts as +0.0.

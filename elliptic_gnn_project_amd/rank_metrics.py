@@ -14,6 +14,22 @@ against the reference's sklearn-based metrics, tests/golden/make_bootstrap_golde
   k clamped to the total weight.  This is the reference's precision_at_k wherever that is defined
   (its unstable argsort leaves a k-th place inside a mixed-label tie group undefined).
 
+The evaluation record (libgnnmp K17, csrc/calibrate.hip) walks the same order.  P / N the included
+positives / negatives; at the end of tie group g with cumulative TP, FP and the group's gTP, gFP:
+prec = TP / (TP + FP), rec = TP / P (1.0 when P = 0, as sklearn), f1 = 2.0*prec*rec/(prec+rec+1e-12)
+in f64 in exactly that operation order (sklearn's precision_recall_curve points, metrics.py's f1):
+
+* max-F1 threshold: the score of the group of largest f1, the lowest score among equals; 1.0 with
+  f1 = 0 without a group (np.nanargmax over the ascending-threshold curve and its appended point);
+* precision-target threshold: the lowest score among groups with prec >= target; without one, 1.0 when
+  1 >= target (the appended point hits), else the max-F1 threshold;
+* recall at precision: the largest rec among groups with prec >= target, else 0.0;
+* ROC-AUC = Σ_g gFP·(2·TP − gTP) / (2·P·N): an integer sum and one f64 division; NaN when P or N is 0;
+* F1 at a threshold: TP, FP, FN of (double)score >= thr, 2TP / (2TP + FP + FN), 0 for a zero denominator;
+  thr must be a float32 value (a score or 1.0), where numpy's f32 comparison agrees with the f64 one;
+* ECE: bin = clip(searchsorted(linspace(0, 1, bins + 1), (double)p, "right") - 1, 0, bins - 1), per bin
+  count, Σy (integers) and Σp (f64), Σ_b cnt_b / n · |Σy_b / cnt_b − Σp_b / cnt_b| over non-empty bins.
+
 The device path keeps its plan and workspace buffers per (device, n, S, slot) and reuses them; a NaN
 score among the included elements sets a bit of a device status word, which ``check_status`` (called
 by default, one scalar read) turns into a ValueError.
@@ -321,3 +337,223 @@ def paired_bootstrap(y, scores_a, scores_b, topk: int, n_boot: int, seed: Option
         return {"delta": float(np.mean(d)), "ci_low": float(lo), "ci_high": float(hi)}
 
     return {"delta_pr_auc": summarize(d_ap), "delta_p_at_k": summarize(d_pk)}
+
+
+# ----------------------------------------------------------------------------- evaluation record (K17)
+ECE_BINS = 15  # metrics.expected_calibration_error's default, the only one the project uses
+RECORD_KEYS = ("pr_auc_illicit", "roc_auc", "f1_illicit_at_thr", "threshold", "precision_at_k", "recall_at_precision",
+               "ece", "n_test")
+
+
+def _f32_threshold(thr) -> float:
+    thr = float(thr)
+    if thr != thr or float(np.float32(thr)) != thr:
+        raise ValueError(f"rank_metrics: threshold {thr!r} is not a float32 value")
+    return thr
+
+
+def _host_curve(s: np.ndarray, y: np.ndarray, target: float) -> Dict[str, float]:
+    """The curve metrics of one segment already in rank order (the module docstring's definitions)."""
+    target = float(target)
+    if target != target:
+        raise ValueError("rank_metrics: precision target is NaN")
+    m = int(s.size)
+    if m == 0:
+        return dict(thr_f1=1.0, f1=0.0, thr_prec=1.0, recall=0.0, roc_auc=float("nan"), P=0, N=0, m=0)
+    y = y.astype(np.int64)
+    s = s + 0.0
+    ends = np.r_[s[1:] != s[:-1], True]
+    TP, FP = np.cumsum(y)[ends], np.cumsum(1 - y)[ends]
+    gTP, gFP = np.diff(TP, prepend=0), np.diff(FP, prepend=0)
+    P, N = int(TP[-1]), int(FP[-1])
+    sc = s[ends].astype(np.float64)
+    prec = TP.astype(np.float64) / (TP + FP).astype(np.float64)
+    rec = TP.astype(np.float64) / float(P) if P > 0 else np.ones(TP.size, dtype=np.float64)
+    f1 = 2.0 * prec * rec / (prec + rec + 1e-12)
+    i = f1.size - 1 - int(np.argmax(f1[::-1]))  # the largest f1, the lowest score among equals
+    hit = np.nonzero(prec >= target)[0]
+    if hit.size:
+        thr_prec, recall = float(sc[hit[-1]]), float(rec[hit].max())
+    else:
+        thr_prec, recall = (1.0 if 1.0 >= target else float(sc[i])), 0.0
+    auc = int(np.sum(gFP * (2 * TP - gTP)))
+    roc = float(auc) / float(2 * P * N) if P > 0 and N > 0 else float("nan")
+    return dict(thr_f1=float(sc[i]), f1=float(f1[i]), thr_prec=thr_prec, recall=recall, roc_auc=roc, P=P, N=N, m=m)
+
+
+def _host_calibration(s: np.ndarray, pos: np.ndarray, inc: np.ndarray, thr: float, bins: int = ECE_BINS) -> Dict:
+    """TP / FP / FN at ``thr``, the calibration bins, f1 and ece of the included elements."""
+    thr = _f32_threshold(thr)
+    p = s[inc].astype(np.float64)
+    y = pos[inc].astype(np.int64)
+    edges = np.linspace(0.0, 1.0, bins + 1)
+    idx = np.clip(np.searchsorted(edges, p, side="right") - 1, 0, bins - 1)
+    cnt = np.bincount(idx, minlength=bins).astype(np.int64)
+    sy = np.bincount(idx, weights=y, minlength=bins).astype(np.int64)
+    sp = np.bincount(idx, weights=p, minlength=bins).astype(np.float64)
+    pred = p >= thr
+    tp, fp, fn = int(np.sum(pred & (y == 1))), int(np.sum(pred & (y == 0))), int(np.sum(~pred & (y == 1)))
+    den = 2 * tp + fp + fn
+    n = int(cnt.sum())
+    ece = 0.0
+    for b in range(bins):
+        c = int(cnt[b])
+        if c:
+            ece += (float(c) / float(n)) * abs(float(sy[b]) / float(c) - float(sp[b]) / float(c))
+    return dict(tp=tp, fp=fp, fn=fn, bin_count=cnt, bin_pos=sy, bin_sum=sp,
+                f1=float(2 * tp) / float(den) if den > 0 else 0.0, ece=float(ece))
+
+
+class _EvalBuffers:
+    """Outputs and workspaces of the K17 calls of one (device, n)."""
+
+    def __init__(self, device: torch.device, n: int):
+        lib = _lib.load()
+        f64, i64 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int64, device=device)
+        self.curve = torch.empty(_lib.CURVE_OUTPUTS, **f64)
+        self.cal = torch.empty(2, **f64)
+        self.counts = torch.empty(3, **i64)
+        self.bin_count = torch.empty(_lib.CALIB_MAX_BINS, **i64)
+        self.bin_pos = torch.empty(_lib.CALIB_MAX_BINS, **i64)
+        self.bin_sum = torch.empty(_lib.CALIB_MAX_BINS, **f64)
+        b = _lib.c_size(0)
+        _lib.check(lib.gnn_rank_curve_workspace_size(n, ctypes.byref(b)), "gnn_rank_curve_workspace_size")
+        self.ws_curve = torch.empty(b.value, dtype=torch.uint8, device=device)
+        _lib.check(lib.gnn_threshold_calibration_workspace_size(n, _lib.CALIB_MAX_BINS, ctypes.byref(b)),
+                   "gnn_threshold_calibration_workspace_size")
+        self.ws_cal = torch.empty(b.value, dtype=torch.uint8, device=device)
+
+
+_EVAL_CACHE: Dict[tuple, _EvalBuffers] = {}
+
+
+def _eval_buffers(device: torch.device, n: int) -> _EvalBuffers:
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n)
+    ev = _EVAL_CACHE.get(key)
+    if ev is None:
+        ev = _EVAL_CACHE[key] = _EvalBuffers(device, n)
+    return ev
+
+
+def _run_curve(buf: _Buffers, ev: _EvalBuffers, positive: torch.Tensor, scores: torch.Tensor, target: float) -> None:
+    _lib.call("gnn_rank_curve", _lib.ptr(buf.order), _lib.ptr(buf.flags), _lib.ptr(buf.seg_ptr), _lib.ptr(positive),
+              _lib.ptr(scores), buf.n, buf.S, float(target), _lib.ptr(ev.curve), _lib.ptr(ev.ws_curve),
+              ev.ws_curve.numel(), _lib.stream_handle(scores.device))
+
+
+def _run_calibration(ev: _EvalBuffers, scores: torch.Tensor, positive: torch.Tensor, inc: Optional[torch.Tensor],
+                     thr: float, bins: int) -> None:
+    if not 1 <= int(bins) <= _lib.CALIB_MAX_BINS:
+        raise ValueError(f"rank_metrics: bins outside [1, {_lib.CALIB_MAX_BINS}]")
+    edges = np.linspace(0.0, 1.0, int(bins) + 1)
+    _lib.call("gnn_threshold_calibration", _lib.ptr(scores), _lib.ptr(positive), _lib.ptr(inc), scores.numel(),
+              _f32_threshold(thr), edges.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(bins),
+              _lib.ptr(ev.counts), _lib.ptr(ev.bin_count), _lib.ptr(ev.bin_pos), _lib.ptr(ev.bin_sum),
+              _lib.ptr(ev.cal), _lib.ptr(ev.ws_cal), ev.ws_cal.numel(), _lib.stream_handle(scores.device))
+
+
+def _device_curve(scores, y, mask, target: float, check: bool):
+    """Plan + curve metrics of the included elements; returns (plan buffers, K17 buffers, operands)."""
+    scores, y, inc = _device_inputs(scores, y, mask)
+    s = scores.detach().to(torch.float32).contiguous()
+    buf = _buffers(s.device, s.numel(), 1)
+    ev = _eval_buffers(s.device, s.numel())
+    _build_plan(buf, s, inc, None)
+    pos = _u8(y == 1)
+    _run_curve(buf, ev, pos, s, target)
+    if check:
+        check_status(buf.status)
+    return buf, ev, s, pos, _u8(inc)
+
+
+def _host_sorted(scores, y, mask):
+    s, pos, inc = _host_inputs(scores, y, mask)
+    o = _host_order(s, inc)
+    return s, pos, inc, o
+
+
+def roc_auc(scores, y, mask=None, check: bool = True):
+    """ROC-AUC of ``y == 1`` over the included elements, 0-dim f64; NaN when only one class is present."""
+    if _is_device(scores, y):
+        return _device_curve(scores, y, mask, 1.0, check)[1].curve[4].clone()
+    s, pos, _, o = _host_sorted(scores, y, mask)
+    return torch.tensor(_host_curve(s[o], pos[o], 1.0)["roc_auc"], dtype=torch.float64)
+
+
+def recall_at_precision(scores, y, precision_target: float, mask=None, check: bool = True):
+    """The best recall among PR-curve points with precision >= target (0.0 without one), 0-dim f64."""
+    if _is_device(scores, y):
+        return _device_curve(scores, y, mask, precision_target, check)[1].curve[3].clone()
+    s, pos, _, o = _host_sorted(scores, y, mask)
+    return torch.tensor(_host_curve(s[o], pos[o], precision_target)["recall"], dtype=torch.float64)
+
+
+def select_threshold(scores, y, mask=None, precision_target: Optional[float] = None) -> Tuple[float, float]:
+    """(decision threshold, the curve's largest F1) as Python floats (device inputs: one read): the
+    precision-target threshold when ``precision_target`` > 0, else the max-F1 threshold
+    (train_gnn._threshold over metrics.pick_threshold_for_precision / pick_threshold_max_f1)."""
+    use_target = bool(precision_target) and float(precision_target) > 0
+    target = float(precision_target) if use_target else 1.0
+    if _is_device(scores, y):
+        buf, ev, *_ = _device_curve(scores, y, mask, target, False)
+        got = torch.cat([ev.curve, buf.status.to(torch.float64)]).cpu()
+        check_status(got[-1:].to(torch.int32))
+        c = dict(thr_f1=float(got[0]), f1=float(got[1]), thr_prec=float(got[2]))
+    else:
+        s, pos, _, o = _host_sorted(scores, y, mask)
+        c = _host_curve(s[o], pos[o], target)
+    return (c["thr_prec"] if use_target else c["thr_f1"]), c["f1"]
+
+
+def _device_calibration(scores, y, mask, thr: float, bins: int) -> _EvalBuffers:
+    scores, y, inc = _device_inputs(scores, y, mask)
+    s = scores.detach().to(torch.float32).contiguous()
+    ev = _eval_buffers(s.device, s.numel())
+    _run_calibration(ev, s, _u8(y == 1), _u8(inc), thr, bins)
+    return ev
+
+
+def f1_at_threshold(scores, y, thr: float, mask=None):
+    """F1 of ``score >= thr`` over the included elements (0 when nothing is predicted or positive), 0-dim f64."""
+    if _is_device(scores, y):
+        return _device_calibration(scores, y, mask, thr, ECE_BINS).cal[0].clone()
+    s, pos, inc = _host_inputs(scores, y, mask)
+    return torch.tensor(_host_calibration(s, pos, inc, thr)["f1"], dtype=torch.float64)
+
+
+def expected_calibration_error(scores, y, mask=None, bins: int = ECE_BINS):
+    """Equal-width-bin ECE of the included elements' positive-class probabilities, 0-dim f64."""
+    if _is_device(scores, y):
+        return _device_calibration(scores, y, mask, 1.0, bins).cal[1].clone()
+    s, pos, inc = _host_inputs(scores, y, mask)
+    return torch.tensor(_host_calibration(s, pos, inc, 1.0, bins)["ece"], dtype=torch.float64)
+
+
+def evaluation_record(scores, y, mask, thr: float, topk: int, precision_target: float) -> Dict:
+    """The eight keys of train_gnn._metrics for the included elements at decision threshold ``thr``; {}
+    for an empty split.  Device inputs: one plan, the AP / P@k walk, the curve walk and the counting
+    pass, every scalar packed into one f64 buffer that is read ONCE together with the status word."""
+    k = int(topk)
+    if k < 1:
+        raise ValueError("evaluation_record: topk < 1")
+    thr = _f32_threshold(thr)
+    if _is_device(scores, y):
+        buf, ev, s, pos, inc = _device_curve(scores, y, mask, precision_target, False)
+        _run_ap(buf, pos, k)
+        _run_calibration(ev, s, pos, inc, thr, ECE_BINS)
+        got = torch.cat([buf.ap[:1], buf.patk[:1], ev.curve, ev.cal, buf.status.to(torch.float64)]).cpu()
+        check_status(got[-1:].to(torch.int32))
+        v = got.tolist()
+        ap, patk, cur, f1, ece = v[0], v[1], v[2:10], v[10], v[11]
+        roc, recall, m = cur[4], cur[3], int(cur[7])
+    else:
+        s, pos, inc, o = _host_sorted(scores, y, mask)
+        m = int(o.size)
+        c = _host_curve(s[o], pos[o], precision_target)
+        cal = _host_calibration(s, pos, inc, thr)
+        ap, patk = _host_ap_sorted(s[o], pos[o])[0], _host_patk_sorted(pos[o], k)
+        roc, recall, f1, ece = c["roc_auc"], c["recall"], cal["f1"], cal["ece"]
+    if m == 0:
+        return {}
+    return dict(pr_auc_illicit=ap, roc_auc=roc, f1_illicit_at_thr=f1, threshold=thr, precision_at_k=patk,
+                recall_at_precision=recall, ece=ece, n_test=m)

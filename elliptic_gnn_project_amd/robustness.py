@@ -209,7 +209,7 @@ def fit_temperature(logits_val: torch.Tensor, y_val: torch.Tensor) -> torch.Tens
 class Run:
     """A run directory loaded once: config, decision threshold, prepared inputs and the best model."""
 
-    def __init__(self, run_dir, processed_dir=None):
+    def __init__(self, run_dir, processed_dir=None, device_eval: Optional[bool] = None):
         from .train_gnn import _model_uses_time_embed, build_model, get_device, load_data
         from .dataset_elliptic import prepare_inputs
         from .planes import register_input
@@ -239,6 +239,8 @@ class Run:
         self.model.eval()
         self.t_idx = self.data.timestep if _model_uses_time_embed(self.model) else None
         self.calibrate = bool(self.cfg.get("calibrate_temperature", True))
+        # the run's ``device_eval`` key unless overridden: temperature fit and record on the device (K17)
+        self.device_eval = bool(self.cfg.get("device_eval", False)) if device_eval is None else bool(device_eval)
         self.y_np = self.data.y.cpu().numpy()
         self.test_np = self.data.test_mask.cpu().numpy().astype(bool)
         self.y_test_bin = (self.y_np[self.test_np] == 1).astype(int)
@@ -246,7 +248,9 @@ class Run:
     def evaluate(self, x: torch.Tensor, edge_index: torch.Tensor, edges_dropped: int, drop_frac: float,
                  noise_std: float, seed: int, details: Optional[Dict] = None) -> Dict:
         """One trial on already perturbed inputs: forward (fp32, no_grad), temperature refit on the
-        validation logits, test metrics.  ``details`` (a dict) receives logits / probs / temperature."""
+        validation logits, test metrics.  ``details`` (a dict) receives logits / probs / temperature.
+        With ``device_eval`` the fit is calibrate.fit_temperature and the record
+        rank_metrics.evaluation_record on the device probabilities (the same keys)."""
         from .train_gnn import _metrics
 
         with torch.no_grad():
@@ -254,13 +258,26 @@ class Run:
         T = None
         vm = self.data.val_mask
         if self.calibrate and bool(vm.any()):
-            T = fit_temperature(logits[vm], self.data.y[vm])
+            if self.device_eval:
+                from .calibrate import fit_temperature as fit_device
+
+                T = fit_device(logits, self.data.y, mask=vm)
+            else:
+                T = fit_temperature(logits[vm], self.data.y[vm])
         with torch.no_grad():
             probs = torch.softmax(logits / T if T is not None else logits, dim=1)[:, 1]
-        p_np = probs.cpu().numpy()
-        if details is not None:
-            details.update(logits=logits, probs=p_np, temperature=T, edge_index=edge_index, x=x)
-        rec = _metrics(self.y_test_bin, p_np[self.test_np], self.threshold, self.cfg)
+        if self.device_eval:
+            from . import rank_metrics
+
+            if details is not None:
+                details.update(logits=logits, probs=probs.cpu().numpy(), temperature=T, edge_index=edge_index, x=x)
+            rec = rank_metrics.evaluation_record(probs, self.data.y, self.data.test_mask, self.threshold,
+                                                 self.cfg.get("topk", 100), self.cfg.get("precision_target", 0.90))
+        else:
+            p_np = probs.cpu().numpy()
+            if details is not None:
+                details.update(logits=logits, probs=p_np, temperature=T, edge_index=edge_index, x=x)
+            rec = _metrics(self.y_test_bin, p_np[self.test_np], self.threshold, self.cfg)
         n0 = int(self.data.edge_index.size(1))
         rec.update(drop_frac_requested=float(drop_frac),
                    drop_frac_effective=float(edges_dropped / n0) if n0 else 0.0,
@@ -275,11 +292,13 @@ class Run:
         return self.evaluate(x, ei, n, drop_frac, noise_std, seed, details)
 
 
-def run(run_dir, drop_frac: float, noise_std: float, seed: int, processed_dir=None) -> Dict:
+def run(run_dir, drop_frac: float, noise_std: float, seed: int, processed_dir=None,
+        device_eval: Optional[bool] = None) -> Dict:
     """The reference's tool for one (drop_frac, noise_std, seed): returns the record and writes it to
-    ``robustness_drop{drop_frac}_noise{noise_std}.json`` in the run directory."""
+    ``robustness_drop{drop_frac}_noise{noise_std}.json`` in the run directory.  ``device_eval`` overrides
+    the run's config key of that name."""
     drop_frac, noise_std = float(drop_frac), float(noise_std)
-    r = Run(run_dir, processed_dir)
+    r = Run(run_dir, processed_dir, device_eval)
     rec = r.trial(drop_frac, noise_std, int(seed))
     with open(r.run_dir / f"robustness_drop{drop_frac}_noise{noise_std}.json", "w", encoding="utf-8") as f:
         json.dump(rec, f, indent=2)
@@ -292,7 +311,7 @@ def _mean_std(vals: List[float]) -> Tuple[float, Optional[float]]:
 
 
 def sweep(run_dir, drop_fracs: Iterable[float], noise_stds: Iterable[float], seeds: Iterable[int],
-          processed_dir=None) -> Dict:
+          processed_dir=None, device_eval: Optional[bool] = None) -> Dict:
     """Every (drop_frac, noise_std, seed) trial over one loaded run: edges dropped once per (seed,
     drop_frac) — one graph plan each — and noise added once per (seed, noise_std).  Returns
     {"records": [one per trial], "summary": [per (drop_frac, noise_std): mean and sample standard
@@ -300,7 +319,7 @@ def sweep(run_dir, drop_fracs: Iterable[float], noise_stds: Iterable[float], see
     drop_fracs = [float(v) for v in drop_fracs]
     noise_stds = [float(v) for v in noise_stds]
     seeds = [int(s) for s in seeds]
-    r = Run(run_dir, processed_dir)
+    r = Run(run_dir, processed_dir, device_eval)
     records = []
     for seed in seeds:
         noisy = {ns: add_noise(r.data.x, ns, seed) for ns in noise_stds}
@@ -334,13 +353,16 @@ def main(argv=None) -> None:
     ap.add_argument("--drop_fracs", type=float, nargs="+", default=None, help="Sweep: the drop fractions")
     ap.add_argument("--noise_stds", type=float, nargs="+", default=None, help="Sweep: the noise levels")
     ap.add_argument("--seeds", type=int, nargs="+", default=None, help="Sweep: the seeds")
+    ap.add_argument("--device_eval", action="store_true", default=None,
+                    help="Temperature fit and metrics on the device (default: the run's device_eval key)")
     args = ap.parse_args(argv)
     if args.drop_fracs is not None or args.noise_stds is not None or args.seeds is not None:
         out = sweep(args.run_dir, args.drop_fracs or [args.drop_frac], args.noise_stds or [args.noise_std],
-                    args.seeds or [args.seed], args.processed_dir)
+                    args.seeds or [args.seed], args.processed_dir, args.device_eval)
         print(json.dumps(out["summary"], indent=2))
     else:
-        print(json.dumps(run(args.run_dir, args.drop_frac, args.noise_std, args.seed, args.processed_dir), indent=2))
+        print(json.dumps(run(args.run_dir, args.drop_frac, args.noise_std, args.seed, args.processed_dir, args.device_eval),
+                         indent=2))
 
 
 if __name__ == "__main__":

@@ -14,7 +14,8 @@ New optional keys: ``synthetic`` (dict of synthetic_elliptic kwargs, used when n
 processed graph exists), ``graph_file`` (PyG-free .npz written by dataset_elliptic.save_graph),
 ``device_metrics`` (default false: validation PR-AUC per epoch and the per-timestep test PR-AUC on the
 device, rank_metrics / libgnnmp K14; full-batch on a CUDA device only — the mini-batch path keeps the
-host metrics).
+host metrics), ``device_eval`` (default false: temperature fit, decision threshold and the metrics.json
+record on the device, calibrate / rank_metrics / libgnnmp K17).
 The mini-batch path (:212-245, :260-276, :329-348) runs on loader.NeighborLoader (K11 sampling).
 """
 from __future__ import annotations
@@ -617,7 +618,13 @@ def main(cfg: Dict) -> Dict:
     validation PR-AUC and the final ``test_pr_auc_by_time`` / ``pr_auc_last{1,3,5}`` are computed on the
     device (rank_metrics, libgnnmp K14) — one scalar crosses to the host per epoch and the best state is
     kept as device clones.  Under ``world_size`` > 1 every rank computes the same value from the gathered
-    logits (no new collective).  The mini-batch path keeps the host metrics whatever the key says."""
+    logits (no new collective).  The mini-batch path keeps the host metrics whatever the key says.
+
+    New optional key ``device_eval`` (default false): the temperature is the minimiser of the validation
+    NLL (calibrate.fit_temperature, one launch) instead of the LBFGS fit, and the decision threshold,
+    ``metrics.json`` and ``metrics_hub_removed.json`` come from the device probabilities through
+    rank_metrics.select_threshold / evaluation_record (libgnnmp K17); files and keys are unchanged.
+    Partitioned runs gather first, as without the key, and T is still broadcast."""
     dist, world, rank = _init_distributed(cfg)
     set_seed(cfg.get("seed", 42))  # same seed on every rank: identical initial weights
     is_main = rank == 0
@@ -665,6 +672,7 @@ def main(cfg: Dict) -> Dict:
                                     input_nodes=data.val_mask.nonzero().view(-1), shuffle=False)
 
     device_metrics = bool(cfg.get("device_metrics", False)) and device.type == "cuda" and not use_mini_batch
+    device_eval = bool(cfg.get("device_eval", False))
     if device_metrics:
         from . import rank_metrics
 
@@ -716,9 +724,15 @@ def main(cfg: Dict) -> Dict:
         _, _, lv = eval_split(model, data, ei, gmask("val_mask"), **ev)
         vm_dev = gmask("val_mask").to(lv.device)
         yv = (gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y)[vm_dev]
-        from .robustness import fit_temperature
+        if device_eval:  # the minimiser of the validation NLL in one launch (calibrate.py, libgnnmp K17)
+            from .calibrate import fit_temperature as fit_device
 
-        T = fit_temperature(lv[vm_dev], yv)
+            y_rows = gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y
+            T = fit_device(lv.float(), y_rows.to(lv.device), mask=vm_dev)
+        else:
+            from .robustness import fit_temperature
+
+            T = fit_temperature(lv[vm_dev], yv)
         if dist is not None:
             dist.broadcast(T, 0)  # one temperature for every rank
 
@@ -742,9 +756,24 @@ def main(cfg: Dict) -> Dict:
     ts = full.timestep.numpy() if dist is not None else data.timestep.cpu().numpy()
     y_val, p_val = (y_np[vm] == 1).astype(int), probs[vm]
     y_te, p_te = (y_np[tm] == 1).astype(int), probs[tm]
-    thr = _threshold(y_val, p_val, cfg) if cfg.get("use_val_for_thresholds", True) \
-        else _max_f1_threshold(y_te, p_te)
-    metrics = _metrics(y_te, p_te, thr, cfg) if y_te.size else {}
+    if device_eval:  # threshold and record from the device probabilities (rank_metrics, libgnnmp K17)
+        from . import rank_metrics as RM
+
+        y_dev = (gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y).to(probs_dev.device)
+        vm_d, tm_d = gmask("val_mask").to(probs_dev.device), gmask("test_mask").to(probs_dev.device)
+        target = cfg.get("precision_target", 0.0)
+        thr = RM.select_threshold(probs_dev, y_dev, vm_d, target)[0] if cfg.get("use_val_for_thresholds", True) \
+            else RM.select_threshold(probs_dev, y_dev, tm_d)[0]
+
+        def record(p_dev):
+            return RM.evaluation_record(p_dev, y_dev, tm_d, thr, cfg.get("topk", 100),
+                                        cfg.get("precision_target", 0.90))
+
+        metrics = record(probs_dev)
+    else:
+        thr = _threshold(y_val, p_val, cfg) if cfg.get("use_val_for_thresholds", True) \
+            else _max_f1_threshold(y_te, p_te)
+        metrics = _metrics(y_te, p_te, thr, cfg) if y_te.size else {}
     metrics["best_val_pr_auc"] = best_val
     if device_metrics:
         y_all = gather_rows(data.y, data.nodes, N, dist) if dist is not None else data.y
@@ -764,8 +793,11 @@ def main(cfg: Dict) -> Dict:
             ei_abl = lei[:, keep_l].to(device)
         else:
             ei_abl = full.edge_index[:, keep].to(device)
-        p_abl = get_probs(ei_abl)[tm]
-        metrics_hub = _metrics(y_te, p_abl, thr, cfg) if y_te.size else {}
+        if device_eval:
+            metrics_hub = record(get_probs_device(ei_abl))
+        else:
+            p_abl = get_probs(ei_abl)[tm]
+            metrics_hub = _metrics(y_te, p_abl, thr, cfg) if y_te.size else {}
         metrics_hub.update(n_hubs=int(num_hubs), hub_fraction=frac, n_edges_remaining=int(keep.sum()))
 
     if is_main:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define GNNMP_ABI_VERSION 31
+#define GNNMP_ABI_VERSION 32
 
 typedef struct ihipStream_t* gnn_stream_t; /* == hipStream_t */
 
@@ -977,6 +977,89 @@ typedef struct {
 } gnn_explain_step_params;
 
 gnn_status gnn_explain_mask_step_f32(const gnn_explain_step_params* p, gnn_stream_t stream);
+
+/* ------------------------------------------------------------------------ */
+/* K17 device evaluation (ABI 32): TemperatureScaler.fit (src/utils/calibrate.py:8-30) as the
+ *     minimiser of the validation NLL, and the host metrics of src/utils/metrics.py:14-66
+ *     (ROC-AUC, max-F1 / precision-target threshold, F1 at a threshold, recall at precision,
+ *     ECE) on the device.  Nothing synchronises or allocates; every call is capturable.       */
+/* ------------------------------------------------------------------------ */
+#define GNN_FIT_THREADS 1024             /* the temperature fit's one workgroup */
+/* bits of the fit's device status word (OR-ed in; the caller zeroes and reads it) */
+#define GNN_FIT_STATUS_LABEL 1           /* an included row's label is outside {0, 1}: it was skipped */
+#define GNN_FIT_STATUS_NAN 2             /* an included row has a NaN or infinite logit: it was skipped */
+#define GNN_FIT_STATUS_EMPTY 4           /* no row to fit: T = 1 */
+#define GNN_FIT_STATUS_FLAT 8            /* |g(1)| <= 1e-7: T = 1 exactly (LBFGS's tolerance_grad exit) */
+#define GNN_FIT_STATUS_CLAMP_LOW 16      /* g(2^-10) >= 0: beta = 2^-10 (T = 1024) */
+#define GNN_FIT_STATUS_CLAMP_HIGH 32     /* g(2^10) <= 0: beta = 2^10 */
+#define GNN_FIT_STATUS_MAXIT 64          /* 100 Newton updates without meeting the step tolerance */
+#define GNN_CURVE_OUTPUTS 8              /* doubles gnn_rank_curve writes */
+#define GNN_CALIB_MAX_BINS 32            /* most calibration bins of gnn_threshold_calibration */
+
+/*
+ * Temperature of two-class logits[n, 2] (f32, row stride ld >= 2 elements) against y[n] (int64) over
+ * the rows with include[i] != 0 (NULL: the rows with y in {0, 1}).  An included row with another label
+ * sets GNN_FIT_STATUS_LABEL, one with a NaN or infinite logit GNN_FIT_STATUS_NAN; both are skipped.
+ * With m_i = (double)z[i, y_i] - (double)z[i, 1 - y_i] over the remaining rows and beta = 1 / T, in f64
+ * with sigma and softplus evaluated through exp(-|t|):
+ *   f(beta) = mean softplus(-beta m_i)     g = -mean m_i sigma(-beta m_i)
+ *   h = mean m_i^2 sigma(beta m_i) sigma(-beta m_i)
+ * Rules, in order: no row -> T = 1, EMPTY; |g(1)| <= 1e-7 -> T = 1, FLAT; g(2^-10) >= 0 -> beta = 2^-10,
+ * CLAMP_LOW; g(2^10) <= 0 -> beta = 2^10, CLAMP_HIGH; else Newton from beta = 1 inside the bracket
+ * g(lo) < 0 < g(hi): the candidate beta - g / h, or the bracket's midpoint when h == 0 or the candidate
+ * is not strictly inside; stop at g == 0, at |beta_new - beta| <= 2^-40 beta (beta_new is kept; a Newton
+ * step |g / h| <= 2^-40 beta stops too, keeping its candidate when strictly inside and beta otherwise), or
+ * after 100 updates (MAXIT).  T[1] (f32) = (float)(1 / beta); diag[4] (f64) = {beta, f(beta), g(beta),
+ * updates made}.  One workgroup of GNN_FIT_THREADS does all of it in one launch: the margins are
+ * compacted into the workspace in row order and every sum runs in one fixed order (bitwise
+ * reproducible).  Workspace: n doubles.  INVALID_ARG before any launch: n < 0, ld < 2, a missing T /
+ * diag / status (or, with n > 0, logits / y); WORKSPACE for a short one.
+ */
+gnn_status gnn_temperature_fit_workspace_size(int64_t n, size_t* bytes);
+gnn_status gnn_temperature_fit(const float* logits, int64_t ld, const int64_t* y, const uint8_t* include,
+                               int64_t n, float* T, double* diag, int32_t* status, void* workspace,
+                               size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * Curve metrics of ONE-segment plan (gnn_rank_plan_build with num_segments = 1; any other value is
+ * INVALID_ARG) over positive[n] (by element) and scores[n] (the plan's scores, to report thresholds).
+ * P / N the included positives / negatives; at the end of tie group g with cumulative TP, FP and the
+ * group's own gTP, gFP: prec = TP / (TP + FP), rec = TP / P (1.0 when P = 0) and
+ * f1 = 2.0 * prec * rec / (prec + rec + 1e-12), each operation rounded in f64 in that order.
+ * out[GNN_CURVE_OUTPUTS] (f64):
+ *   [0] max-F1 threshold: the score of the group of largest f1, the lowest score among equals (1.0
+ *       without a group)                                  [1] that f1 (0.0 without a group)
+ *   [2] precision-target threshold: the lowest score among groups with prec >= target_precision; without
+ *       one, 1.0 when 1 >= target_precision, else out[0]
+ *   [3] recall at precision: the largest rec among groups with prec >= target_precision, 0.0 without one
+ *   [4] ROC-AUC = sum_g gFP (2 TP - gTP) / (2 P N): an int64 sum and one f64 division; NaN when P or N is 0
+ *   [5] P   [6] N   [7] the included elements
+ * The argmax reductions compare (value, position) exactly: bitwise reproducible whatever their order.
+ */
+gnn_status gnn_rank_curve_workspace_size(int64_t n, size_t* bytes);
+gnn_status gnn_rank_curve(const int32_t* order, const uint8_t* flags, const int32_t* seg_ptr,
+                          const uint8_t* positive, const float* scores, int64_t n, int64_t num_segments,
+                          double target_precision, double* out, void* workspace, size_t workspace_bytes,
+                          gnn_stream_t stream);
+
+/*
+ * One pass over scores[n] (f32), positive[n], include[n] (NULL = all), no sort: counts[3] (int64) =
+ * TP, FP, FN of (double)score >= thr; per bin b of the `bins` (1 .. GNN_CALIB_MAX_BINS) bins given by
+ * edges[bins + 1] (HOST array, ascending f64, read during the call), with
+ * bin = clip(#{edges <= (double)score} - 1, 0, bins - 1) (numpy's searchsorted side="right"):
+ * bin_count[b], bin_pos[b] (int64) and bin_sum[b] = sum of (double)score (f64, one fixed order).
+ * out[2] (f64) = {f1 = 2 TP / (2 TP + FP + FN) (0 when the denominator is 0),
+ * ece = sum over non-empty bins of bin_count / n * |bin_pos / bin_count - bin_sum / bin_count|}.
+ * thr must be a float32 value (every threshold of the pipeline is a score or 1.0; numpy's f32
+ * comparison and this f64 one then agree).  INVALID_ARG before any launch: n < 0, bins out of range,
+ * a missing pointer, thr not a float32 value, descending edges; WORKSPACE for a short one.
+ */
+gnn_status gnn_threshold_calibration_workspace_size(int64_t n, int32_t bins, size_t* bytes);
+gnn_status gnn_threshold_calibration(const float* scores, const uint8_t* positive, const uint8_t* include,
+                                     int64_t n, double thr, const double* edges, int32_t bins,
+                                     int64_t* counts, int64_t* bin_count, int64_t* bin_pos, double* bin_sum,
+                                     double* out, void* workspace, size_t workspace_bytes,
+                                     gnn_stream_t stream);
 
 #ifdef __cplusplus
 }
