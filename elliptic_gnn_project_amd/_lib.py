@@ -471,6 +471,11 @@ SIGNATURES = {
         ctypes.c_int,
         [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_double, ctypes.POINTER(ctypes.c_double), c_i32, c_ptr, c_ptr, c_ptr,
          c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    # K18 (additive to ABI 32)
+    "gnn_hub_rank_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_hub_rank": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_hub_ablate_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_hub_ablate": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

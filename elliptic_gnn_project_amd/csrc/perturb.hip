@@ -19,6 +19,7 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "common.hpp"
+#include "edge_compact.hpp"
 
 namespace gnnmp {
 namespace {
@@ -60,16 +61,6 @@ __global__ void drop_flags_kernel(const int32_t* __restrict__ order, int64_t E, 
   keep[order[t]] = t >= drop_count ? 1 : 0;
 }
 
-__global__ void drop_compact_kernel(const int64_t* __restrict__ ei, int64_t E, int64_t kept,
-                                    const int32_t* __restrict__ keep, const int32_t* __restrict__ pos,
-                                    int64_t* __restrict__ out) {
-  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (e >= E || !keep[e]) return;
-  const int64_t p = pos[e];  // < kept: the number of kept edges before e
-  out[p] = ei[e];
-  out[kept + p] = ei[E + e];
-}
-
 struct DropLayout {
   uint32_t *hash, *hash_out;
   int32_t *eid, *order;
@@ -84,9 +75,8 @@ gnn_status drop_tmp_bytes(int64_t E, size_t* bytes) {
   hipError_t err = rocprim::radix_sort_pairs(nullptr, sb, (uint32_t*)nullptr, (uint32_t*)nullptr, (int32_t*)nullptr,
                                              (int32_t*)nullptr, n, 0, 32, (hipStream_t)0);
   if (err != hipSuccess) return hip_check(err, "drop_tmp_bytes (sort)");
-  err = rocprim::exclusive_scan(nullptr, tb, (const int32_t*)nullptr, (int32_t*)nullptr, 0, n,
-                                rocprim::plus<int32_t>(), (hipStream_t)0);
-  if (err != hipSuccess) return hip_check(err, "drop_tmp_bytes (scan)");
+  gnn_status s = edge_compact_tmp_bytes(E, (const int32_t*)nullptr, &tb);
+  if (s != GNN_OK) return s;
   *bytes = sb > tb ? sb : tb;
   return GNN_OK;
 }
@@ -203,11 +193,9 @@ extern "C" gnn_status gnn_edge_drop(const int64_t* edge_index, int64_t num_edges
   GNN_HIP_TRY(rocprim::radix_sort_pairs(L.tmp, sb, L.hash, L.hash_out, L.eid, L.order, (size_t)E, 0, 32, st));
   drop_flags_kernel<<<nb, kTB, 0, st>>>(L.order, E, drop_count, L.keep);
   GNN_LAUNCH_CHECK();
-  sb = L.tmp_bytes;
-  GNN_HIP_TRY(rocprim::exclusive_scan(L.tmp, sb, L.keep, L.pos, 0, (size_t)E, rocprim::plus<int32_t>(), st));
-  drop_compact_kernel<<<nb, kTB, 0, st>>>(edge_index, E, E - drop_count, L.keep, L.pos, out);
-  GNN_LAUNCH_CHECK();
-  return GNN_OK;
+  // exclusive scan of the flags and compaction of both rows (edge_compact.hpp, shared with hub.hip)
+  return edge_compact(edge_index, E, E - drop_count, (const int32_t*)L.keep, KeepFlag{L.keep}, L.pos, L.tmp, L.tmp_bytes,
+                      out, st);
 }
 
 extern "C" gnn_status gnn_feature_noise_f32(const float* x, int64_t ldx, int64_t rows, int64_t F, float noise_std,

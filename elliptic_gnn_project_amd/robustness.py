@@ -206,10 +206,23 @@ def fit_temperature(logits_val: torch.Tensor, y_val: torch.Tensor) -> torch.Tens
 
 
 # ----------------------------------------------------------------------------- a trained run
+def check_feature_width(model: torch.nn.Module, state: Dict, in_dim: int) -> None:
+    """ValueError naming both widths when ``state`` (a checkpoint) was trained on another feature width
+    than the ``in_dim`` columns ``model`` was built for: the first weight matrix of equal rows whose
+    column counts differ gives the checkpoint's width.  (The reference's hub ablation pads or truncates
+    the features instead, _align_features_to_model; inputs here come from the run's own config.)"""
+    for k, w in model.state_dict().items():
+        s = state.get(k)
+        if s is not None and w.dim() == 2 and s.dim() == 2 and w.size(0) == s.size(0) and w.size(1) != s.size(1):
+            raise ValueError(f"the checkpoint expects {int(in_dim) + int(s.size(1)) - int(w.size(1))} input features "
+                             f"({k}: {tuple(s.shape)}), the prepared graph has {int(in_dim)}; features are not "
+                             "padded or truncated")
+
+
 class Run:
     """A run directory loaded once: config, decision threshold, prepared inputs and the best model."""
 
-    def __init__(self, run_dir, processed_dir=None, device_eval: Optional[bool] = None):
+    def __init__(self, run_dir, processed_dir=None, device_eval: Optional[bool] = None, check_width: bool = False):
         from .train_gnn import _model_uses_time_embed, build_model, get_device, load_data
         from .dataset_elliptic import prepare_inputs
         from .planes import register_input
@@ -235,7 +248,10 @@ class Run:
         self.data = prepare_inputs(load_data(cfg), cfg).to(self.device)  # as train_gnn.main prepares them
         register_input(self.data.x)  # the unperturbed features are the run's constant input, as in main
         self.model = build_model(cfg["arch"], self.data.x.size(1), cfg).to(self.device)
-        self.model.load_state_dict(torch.load(self.run_dir / "best.ckpt", map_location=self.device, weights_only=True))
+        state = torch.load(self.run_dir / "best.ckpt", map_location=self.device, weights_only=True)
+        if check_width:
+            check_feature_width(self.model, state, int(self.data.x.size(1)))
+        self.model.load_state_dict(state)
         self.model.eval()
         self.t_idx = self.data.timestep if _model_uses_time_embed(self.model) else None
         self.calibrate = bool(self.cfg.get("calibrate_temperature", True))

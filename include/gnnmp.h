@@ -1061,6 +1061,40 @@ gnn_status gnn_threshold_calibration(const float* scores, const uint8_t* positiv
                                      double* out, void* workspace, size_t workspace_bytes,
                                      gnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* K18 hub ablation (additive to ABI 32: new symbols only, no struct touched): the degree ranking
+ *     and nested edge ablation of src/analysis/hub_ablation.py:56-71 (build_edge_index_ablated)  */
+/* ------------------------------------------------------------------------ */
+/*
+ * gnn_hub_rank: for edge_index[2, E] (contiguous int64, ids in [0, N), TRUSTED: the caller checks them)
+ *   deg[v]         = #{e : src[e] = v} + #{e : dst[e] = v}   (a self loop counts 2, duplicates each time)
+ *   order[N]       = the nodes by (deg descending, node id ascending);   rank[N] = its inverse
+ *   edge_rank[e]   = min(rank[src[e]], rank[dst[e]])
+ *   removed_cum[r] = #{e : edge_rank[e] <= r}
+ * all int32 (deg is an unsigned count: deg <= 2 E < 2^32).  Integer atomics, one stable radix sort:
+ * bitwise reproducible.  torch.topk leaves the order of equal degrees unspecified; this tie rule (lower
+ * id first) gives topk's set exactly when deg[order[h-1]] > deg[order[h]].  num_edges = 0 launches
+ * nothing and writes nothing.  INVALID_ARG before any launch: a negative size, num_edges or num_nodes
+ * >= INT32_MAX, edges without nodes, a null buffer; WORKSPACE for a missing or short one.
+ *
+ * gnn_hub_ablate: out[2, kept] = the columns e of edge_index with edge_rank[e] >= num_hubs, in input
+ * order: the graph without every edge that touches one of order[0 .. num_hubs).  `kept` is the caller's
+ * E - removed_cum[num_hubs - 1], as gnn_edge_drop's E - drop_count: no host synchronisation,
+ * capturable; a column whose output position is not below `kept` is not written.  num_edges = 0,
+ * num_hubs = 0 (the caller keeps edge_index itself) and kept = 0 launch nothing.  INVALID_ARG before any
+ * launch: negative num_edges, num_edges >= INT32_MAX, num_hubs outside [0, INT32_MAX) (the ranking's
+ * num_nodes, below INT32_MAX, is not an argument here: the caller holds num_hubs <= num_nodes), kept
+ * outside [0, num_edges], a null buffer; WORKSPACE for a missing or short one.
+ */
+gnn_status gnn_hub_rank_workspace_size(int64_t num_nodes, int64_t num_edges, size_t* bytes);
+gnn_status gnn_hub_rank(const int64_t* edge_index, int64_t num_edges, int64_t num_nodes, int32_t* deg,
+                        int32_t* order, int32_t* rank, int32_t* edge_rank, int32_t* removed_cum,
+                        void* workspace, size_t workspace_bytes, gnn_stream_t stream);
+gnn_status gnn_hub_ablate_workspace_size(int64_t num_edges, size_t* bytes);
+gnn_status gnn_hub_ablate(const int64_t* edge_index, int64_t num_edges, const int32_t* edge_rank,
+                          int64_t num_hubs, int64_t kept, int64_t* out, void* workspace,
+                          size_t workspace_bytes, gnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
