@@ -357,6 +357,8 @@ SIGNATURES = {
     "gnn_gemm_tn_f32": (ctypes.c_int, [ctypes.POINTER(GnnGemmTNParams), c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_gemm_tn_active_f32": (ctypes.c_int, [ctypes.POINTER(GnnGemmTNParams), c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_gemm_tn_active_pays": (ctypes.c_int, [c_i64]),
+    "gnn_gemm_tn_active_split": (ctypes.c_int, []),
+    "gnn_gemm_tn_active_ring": (ctypes.c_int, []),
     "gnn_gemm_nt_planes_ok": (ctypes.c_int, [ctypes.POINTER(GnnGemmNTParams)]),
     "gnn_gemm_nt_colsum_blocks": (ctypes.c_int, [ctypes.POINTER(GnnGemmNTParams), ctypes.POINTER(c_i32)]),
     "gnn_colsum_finish_f32": (ctypes.c_int, [c_ptr, c_i32, c_i64, c_ptr, c_ptr]),

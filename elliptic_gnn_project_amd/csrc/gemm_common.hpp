@@ -196,6 +196,10 @@ struct TNArgs {
   // (ABI 28) the half-pair dz form: one byte per GNN_ACTIVE_ROWS rows of dz, 0 = the group's dz rows
   // are all zero (each block walks only the flagged chunks of its row block); null: every chunk
   const uint8_t* dz_active;
+  // with dz_active: the slab's last word (slab_stride - 1, a pad word: slab_stride > the outputs)
+  // holds 1 where the row block had no flagged chunk and wrote nothing else, else 0; 0: every
+  // block writes its whole slab (launch_slab_reduce's `empty`)
+  int32_t slab_empty;
 };
 // the most 16-row chunks a row block of the flag-driven TN holds (tn_h2_ok bounds M below 1.6 M
 // rows: 2 · ceil(ceil(M / 32) / 256) <= 392); at most one per thread of its 512
@@ -207,9 +211,10 @@ void launch_nt_f32(const NTArgs& a, int avec, hipStream_t st);  // avec: widest 
 void launch_tn_f32(const TNArgs& a, int nblk, hipStream_t st);
 constexpr int kRedOut = 16;  // float4 outputs per block of the reduce
 // out[j] = Σ_{b < nred} slab[b · stride + j], j < n_out; sq: the call's params when they ask for the
-// norm partials of out (sq_partial, ABI 20), else null
+// norm partials of out (sq_partial, ABI 20), else null; empty: the slabs carry the flag-driven TN's
+// "nothing written" word (TNArgs::slab_empty) and those that say so are skipped, not read
 void launch_slab_reduce(const float* slab, int64_t stride, int nred, float* out, int64_t n_out,
-                        const gnn_gemm_tn_params* sq, hipStream_t st);
+                        const gnn_gemm_tn_params* sq, hipStream_t st, bool empty = false);
 
 // split-bf16 ("x3": each f32 operand = hi + mid + lo bf16, 6 MFMA products) launchers,
 // defined in gemm_x3.hip.  Only the w1/w2 (in-place Linear weight) B form runs split.
@@ -247,7 +252,9 @@ gnn_status nt_h2_prep_from_params(const gnn_gemm_nt_params* p, H2Prep* out, cons
 void launch_nt_h2(const NTArgs& a, uint4* img, hipStream_t st, int phase = NT_PHASE_ALL);
 void launch_prep_h2(const H2Prep& p, hipStream_t st);  // ws_prep_h2_kernel over p (gemm_ws.hip)
 bool tn_h2_ok(const TNArgs& a);
-void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks = false);
+// the flag-driven form's column blocks per row block and the chunks of loads each keeps in flight
+constexpr int TN_ACT_SPLIT = 4, TN_ACT_RING = 1;
+void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks = false, bool act_split = false);
 bool tn_planes_ok(const TNArgs& a);
 void launch_tn_planes(const TNArgs& a, int nblk, hipStream_t st);
 bool tn_img16_ok(const TNArgs& a);

@@ -290,6 +290,17 @@ bool tn_csc_in_kernel(int64_t rows_per_block) {
 // the call-side one and GNNMP_TN_CSC=0 all reach the same kernel)
 bool tn_active_pays(int64_t M) { return M >= 16 && !tn_wave_per_group(tn_dz_rows(M).rows); }
 int64_t tn_active_bytes(int64_t M) { return (ceil_div(M, GNN_ACTIVE_ROWS) + 15) / 16 * 16; }
+// The flag-driven TN's form, read at every call (A/B inside one process):
+// GNNMP_TN_ACTIVE_SPLIT=0 runs its first form — one block per row block, one chunk of loads in
+// flight — instead of TN_ACT_SPLIT column blocks per row block with loads TN_ACT_RING chunks deep;
+// GNNMP_TN_EMPTY_SKIP=0 has the row blocks without a flagged chunk write their zero slabs and the
+// reduce read them.  Every combination gives the same bits.
+bool env_off(const char* name) {
+  const char* e = std::getenv(name);
+  return e && e[0] == '0' && !e[1];
+}
+bool tn_active_split() { return !env_off("GNNMP_TN_ACTIVE_SPLIT"); }
+bool tn_empty_skip() { return !env_off("GNNMP_TN_EMPTY_SKIP"); }
 
 // floats of a TN output: dW[Nr][Kc] | db[Nr] | dW2[nproj][Nr] | dzsum[nproj]; a slab holds them padded
 int64_t tn_out_floats(int64_t Nr, int64_t Kc, int32_t nproj) { return Nr * Kc + Nr + (int64_t)nproj * Nr + nproj; }
@@ -345,6 +356,8 @@ struct TNPlan {
   int blocks, nred;        // the launch's grid; the slabs it writes
   int64_t rows_per_block;
   bool ksplit;             // split-K block pairs: blocks = 2 nred
+  bool act_split;          // flags: TN_ACT_SPLIT column blocks per row block: blocks = TN_ACT_SPLIT nred
+  bool empty;              // flags: unflagged row blocks write their slab's empty word only, the reduce skips them
   TNCsc csc;               // CALL_SIDE: gnn_aggregate_active_f32 first
   TNFlags flags;           // dz's activity flags; WORKSPACE: at flags_off, written by the call-side CSC sum
   size_t flags_off;
@@ -396,6 +409,13 @@ TNPlan tn_plan(const gnn_gemm_tn_params* p, const TNArgs& a, size_t ws_bytes, co
         return no(GNN_ERR_UNSUPPORTED, "dz_active: row block beyond the chunk list's capacity");
       pl.ksplit = a.dz && a.M <= tn_ksplit_max_m() && pl.flags == TN_FLAGS_NONE;
       if (pl.ksplit) pl.blocks = 2 * pl.nred;
+      if (pl.flags != TN_FLAGS_NONE) {
+        pl.act_split = tn_active_split();
+        if (pl.act_split) pl.blocks = TN_ACT_SPLIT * pl.nred;
+        // the empty word is the slab's last pad word (no workspace beyond the slabs): a shape whose
+        // outputs fill the stride has none and writes every slab
+        pl.empty = tn_empty_skip() && a.slab_stride > tn_out_floats(a.Nr, a.k1 + a.k2, a.nproj);
+      }
       return run(TN_IMG_H2);
     }
     if (planes_only) return no(GNN_ERR_UNSUPPORTED, "half-pair image A outside the half-pair kernel's shapes");
@@ -467,10 +487,11 @@ gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* works
   }
   a.rows_per_block = pl.rows_per_block;
   a.dz_active = pl.flags == TN_FLAGS_CALLER ? dz_active : ws_flags;
+  a.slab_empty = pl.empty;
   if (pl.kernel >= TN_SKINNY) a.ap = nullptr;      // the f32 operands serve ...
   if (pl.kernel <= TN_SKINNY) a.rowexp = nullptr;  // ... and only the MFMA kernels over them read their row exponents
   switch (pl.kernel) {
-    case TN_IMG_H2: launch_tn_h2(a, pl.blocks, st, pl.ksplit); break;
+    case TN_IMG_H2: launch_tn_h2(a, pl.blocks, st, pl.ksplit, pl.act_split); break;
     case TN_IMG_BF16: launch_tn_img16(a, pl.blocks, st); break;
     case TN_IMG_SPLIT: launch_tn_planes(a, pl.blocks, st); break;
     case TN_SKINNY: launch_tn_skinny(a, pl.blocks, st); break;
@@ -479,7 +500,7 @@ gnn_status gemm_tn_dispatch(const gnn_gemm_tn_params* p, float* out, void* works
     case TN_F32: launch_tn_f32(a, pl.blocks, st); break;
   }
   if (const gnn_status s = hip_check(hipGetLastError(), fn)) return s;
-  launch_slab_reduce(a.slab, a.slab_stride, pl.nred, out, n_out, p, st);
+  launch_slab_reduce(a.slab, a.slab_stride, pl.nred, out, n_out, p, st, pl.empty);
   return hip_check(hipGetLastError(), fn);
 }
 
@@ -497,6 +518,8 @@ extern "C" gnn_status gnn_gemm_tn_workspace_size(int64_t M, int64_t Nr, int64_t 
 }
 
 extern "C" int gnn_gemm_tn_active_pays(int64_t M) { return tn_active_pays(M) ? 1 : 0; }
+extern "C" int gnn_gemm_tn_active_split(void) { return TN_ACT_SPLIT; }
+extern "C" int gnn_gemm_tn_active_ring(void) { return TN_ACT_RING; }
 extern "C" gnn_status gnn_gemm_tn_sq_blocks(int64_t n_out, int32_t* nb) {
   if (!nb || n_out < 1) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
   *nb = (int32_t)red_blocks(n_out);

@@ -684,6 +684,9 @@ struct SqOut {
   float* part; const float* step; int64_t skip_lo, skip_hi;
 };
 constexpr int kRedGrp = 16;
+// EMPTY: the slabs carry the flag-driven TN's empty word (an instantiation of its own: the plain
+// form keeps its registers)
+template <bool EMPTY>
 __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restrict__ slab, int64_t stride, int nblk,
                                                           float* __restrict__ out, int64_t n, SqOut sq = SqOut{}) {
   __shared__ float4 part[kRedGrp][kRedOut];
@@ -693,7 +696,31 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   const int per = (nblk + kRedGrp - 1) / kRedGrp;
   const int b0 = g * per, b1 = min(nblk, b0 + per);
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (j < n) {
+  if (j < n && EMPTY) {
+    // the flag-driven TN's slabs: the last word of a slab is 1 where its row block wrote nothing
+    // else (TNArgs::slab_empty).  Such a slab is not read — its memory is stale — and nothing is
+    // added for it: it would have held +0.0f everywhere, and s starts at +0.0f and never becomes
+    // -0.0f (x + y is -0.0f only for two negative zeros), so s + (+0.0f) == s bit for bit.  The
+    // group's slabs are still added in order; 16 at a time have their words, then their loads, in
+    // flight together.
+    for (int bb = b0; bb < b1; bb += 16) {
+      uint32_t live = 0;
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const uint32_t w = reinterpret_cast<const uint32_t*>(slab)[(int64_t)min(bb + u, b1 - 1) * stride + stride - 1];
+        live |= (bb + u < b1 && w == 0u) ? 1u << u : 0u;
+      }
+      float4 v[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (live >> u & 1) v[u] = *reinterpret_cast<const float4*>(slab + (int64_t)(bb + u) * stride + j);
+#pragma unroll
+      for (int u = 0; u < 16; ++u)
+        if (live >> u & 1) {
+          s.x += v[u].x; s.y += v[u].y; s.z += v[u].z; s.w += v[u].w;
+        }
+    }
+  } else if (j < n) {
     int b = b0;
     for (; b + 4 <= b1; b += 4) {
       float4 v0 = *reinterpret_cast<const float4*>(slab + (int64_t)(b + 0) * stride + j);
@@ -774,9 +801,11 @@ void launch_tn_f32(const TNArgs& a, int nblk, hipStream_t st) {
 }
 
 void launch_slab_reduce(const float* slab, int64_t stride, int nred, float* out, int64_t n_out,
-                        const gnn_gemm_tn_params* sq, hipStream_t st) {
+                        const gnn_gemm_tn_params* sq, hipStream_t st, bool empty) {
   const SqOut sqo = sq && sq->sq_partial ? SqOut{sq->sq_partial, sq->sq_step, sq->sq_skip_lo, sq->sq_skip_hi} : SqOut{};
-  slab_reduce_kernel<<<(unsigned)ceil_div(ceil_div(n_out, 4), kRedOut), 256, 0, st>>>(slab, stride, nred, out, n_out, sqo);
+  const unsigned nb = (unsigned)ceil_div(ceil_div(n_out, 4), kRedOut);
+  if (empty) slab_reduce_kernel<true><<<nb, 256, 0, st>>>(slab, stride, nred, out, n_out, sqo);
+  else slab_reduce_kernel<false><<<nb, 256, 0, st>>>(slab, stride, nred, out, n_out, sqo);
 }
 
 }  // namespace gnnmp

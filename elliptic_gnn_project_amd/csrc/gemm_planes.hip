@@ -588,15 +588,25 @@ __device__ __forceinline__ float tn_csc_fold(const TNArgs& a, int64_t mbeg, int6
 // f32 sums, and Adam grows that 1e-7 difference to 1e-3 in the logits within 25 steps.)
 // Unflagged chunks are never read: a non-finite A or h row there no longer reaches dW (the dense
 // product's 0 · NaN).
-template <int KT, bool GOUT, int LAB = 0, int NW = 4, bool GF = false, int KS = 1, bool CSC = false, bool ACT = false>
+// ACT with KS = 2 .. 4: the split-K scheme over the busy row blocks — KS blocks per row block, each
+// with a contiguous k-tile range.  All of them build the same chunk list from the same flags, form
+// the same G with the same s_b and write their columns of the row block's one slab (the side sums
+// come from the first), so each accumulator element sees its row block's chunks in the dense order
+// with the dense scale: the same bits again, and the slab count is the dense call's.  RD: the
+// register ring's depth (lab only: deeper rings measured slower in every form,
+// profiles/tn_active_split_lab.txt).
+template <int KT, bool GOUT, int LAB = 0, int NW = 4, bool GF = false, int KS = 1, bool CSC = false, bool ACT = false,
+          int RD = 1>
 __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   static_assert(NW == 4 || NW == 8, "4 or 8 waves");
-  static_assert(KS == 1 || (KS == 2 && NW == 8), "split-K: the 8-wave form");
-  static_assert(!ACT || (NW == 8 && !GOUT && !GF && KS == 1 && !CSC && !(LAB & 16)), "ACT: the plain dz form");
+  static_assert(KS == 1 || (KS == 2 && NW == 8) || (ACT && KS <= 4), "split-K: the 8-wave form (ACT: up to 4 ways)");
+  static_assert(!ACT || (NW == 8 && !GOUT && !GF && !CSC && !(LAB & 16)), "ACT: the plain dz form");
+  static_assert(RD == 1 || (ACT && RD <= 4), "the deep register ring: the flag-driven form");
   constexpr int T = 64 * NW;
-  constexpr int NPA = (2 * PT_ROWS * (PT_MAXLD / 8) + T - 1) / T;  // A pieces per thread per chunk (6 / 3)
+  constexpr int KTB = (KT + KS - 1) / KS;                            // k-tiles of a block (at most)
+  // A pieces per thread per chunk (6 / 3; the column-split ACT blocks hold only their k-range's: 2 / 1)
+  constexpr int NPA = ((ACT && KS > 1 ? 2 * PT_ROWS * 4 * KTB : 2 * PT_ROWS * (PT_MAXLD / 8)) + T - 1) / T;
   constexpr int RP = PT_ROWS / (T / 128);                           // G rows per thread per chunk (8 / 4)
-  constexpr int KTB = KS == 1 ? KT : (KT + 1) / 2;                   // k-tiles of a block (at most)
   constexpr int KTW = NW == 4 ? KTB : (KTB + 1) / 2;                // k-tiles per wave
   __shared__ __attribute__((aligned(16))) uint16_t Gt[2][3 * PT_GPL];
   __shared__ __attribute__((aligned(16))) uint16_t At[2][2 * PT_APL];
@@ -609,18 +619,24 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   // A's register ring: RING sets of the NPA pieces, a chunk's loads issued RING chunks before
   // its LDS put.  LAB 16: two sets — measured slower (lab 104.2 vs 100.6 us, r18h: the second
   // set's 24 VGPRs cost more in the chunk loop than the extra lead buys)
-  constexpr int RING = (LAB & 16) ? 2 : 1;
+  // RD (ACT, lab): RD sets of A pieces, G rows and dz values — the loads of chunks c + 2 .. c + 1 + RD
+  // in flight during chunk c.  Measured slower at every split (71.6 -> 73.4 / 74.8 us at RD = 2 / 3
+  // unsplit, 59.1 -> 61.4 / 63.0 / 61.8 at KS = 4): the chunk step is not a load round trip
+  constexpr int RING = (LAB & 16) ? 2 : RD;
   // RGN: register sets of G rows (2: two chunks ahead; measured no faster on the g form, r27: 70.0
   // vs 66.9 us on the GCN layer-1 shape, so one set)
-  constexpr int RGN = 1;
+  constexpr int RGN = RD;
+  constexpr int RZ = RD;  // registers of the dz ring (chunk k's value in slot k % RZ)
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int ld = a.ap_ld;
-  const int kpart = KS == 1 ? 0 : (int)(blockIdx.x & 1);   // split-K: this block's k-range
-  const int rblk = KS == 1 ? (int)blockIdx.x : (int)(blockIdx.x >> 1);
-  const int kt0 = kpart * KTB;                              // first k-tile
-  const int ktb = KS == 1 ? KT : (kpart ? KT - KTB : KTB);  // k-tiles of this block
+  // split-K: blocks KS·b .. KS·b + KS - 1 take row block b and the k-tiles [kt0, kt0 + ktb), KT
+  // dealt as evenly as it goes, the longer ranges first (KS = 2: 6 + 5; 3: 4 + 4 + 3; 4: 3 + 3 + 3 + 2)
+  const int kpart = KS == 1 ? 0 : (int)(blockIdx.x % KS);
+  const int rblk = KS == 1 ? (int)blockIdx.x : (int)(blockIdx.x / KS);
+  const int kt0 = (kpart * KT + KS - 1) / KS;                    // first k-tile
+  const int ktb = ((kpart + 1) * KT + KS - 1) / KS - kt0;        // k-tiles of this block
   const int pr = min(4 * ktb, (ld - 32 * kt0) >> 3);        // 16-byte A pieces per row
   const int64_t mbeg = (int64_t)rblk * a.rows_per_block;
   const int64_t mend = min(a.M, mbeg + a.rows_per_block);
@@ -648,6 +664,16 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     if (on && pos < TN_ACT_CAP) clist[pos] = q;
     __syncthreads();
     nch = min(n_act, TN_ACT_CAP);
+    // a.slab_empty: the last pad word of the row block's slab says whether the slab was written.  A
+    // row block without a flagged chunk writes only that word — no zero slab, no side sums — and the
+    // reduce skips the slab: it would have added +0.0f (0 · gunsc) to sums that start at +0.0f and
+    // can never become -0.0f, which changes no bit.  (Every column block of a row block sees the
+    // same flags; the first one writes the word.)
+    if (a.slab_empty) {
+      if (kpart == 0 && tid == 0)
+        reinterpret_cast<uint32_t*>(a.slab + (int64_t)rblk * a.slab_stride)[a.slab_stride - 1] = nch == 0 ? 1u : 0u;
+      if (nch == 0) return;
+    }
   }
   typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
   const int wrow = 32 * (wave & 3);                             // this wave's dW rows
@@ -809,10 +835,11 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   // rows, read from the list once at the top of chunk c (the staging units then hold no LDS read)
   // glo: the first own row of the chunk whose G rows are being formed — a shifted-back tail chunk
   // re-loads rows of the chunk before it, which may be unflagged: their h must not reach dzᵀ·h
+  // (RD > 1: ab2 is chunk min(c + 1 + RD, clast)'s base, ab3 chunk min(c + 2 + RD, clast)'s)
   int ab2 = 0, ab3 = 0, az2lo = 0, az2hi = 0, glo = 0;
   u32x4 ra[RING][NPA];
   float rg[RGN][RP];
-  float rz = 0.f;
+  float rz[RZ] = {};
   auto load_a_at = [&](int s, int j, int mb) __attribute__((always_inline)) {
     ra[s][j] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, (int)goff[j], mb * ld * 2, 0);
   };
@@ -826,10 +853,10 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     }
   };
   auto load_g = [&](int sg, int c) __attribute__((always_inline)) { load_g_at(sg, ldbase(c)); };
-  auto load_z_at = [&](int mb) __attribute__((always_inline)) {
-    if constexpr (!GF) rz = a.dz[(uint32_t)((mb + zr) * (int)a.lddz + zqc)];
+  auto load_z_at = [&](int sz, int mb) __attribute__((always_inline)) {
+    if constexpr (!GF) rz[sz] = a.dz[(uint32_t)((mb + zr) * (int)a.lddz + zqc)];
   };
-  auto load_z = [&](int c) __attribute__((always_inline)) { load_z_at(ldbase(c)); };
+  auto load_z = [&](int sz, int c) __attribute__((always_inline)) { load_z_at(sz, ldbase(c)); };
   auto put_zlh = [&](int k, int lo, int hi, float v) __attribute__((always_inline)) {
     if constexpr (GF) return;
     const bool ok = tid < PT_ROWS * MAXPROJ && zq < a.nproj && zr >= lo && zr < hi;
@@ -841,7 +868,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     zrange(k, lo, hi);
     put_zlh(k, lo, hi, v);
   };
-  auto put_z = [&](int k) __attribute__((always_inline)) { put_zv(k, rz); };
+  auto put_z = [&](int k) __attribute__((always_inline)) { put_zv(k, rz[0]); };
 
   float db = 0.f, dzs = 0.f;
   float dw2[MAXPROJ] = {0.f, 0.f, 0.f, 0.f};
@@ -912,15 +939,16 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
   };
   // staging unit k of chunk c + 1 (refills for chunks c + 2 / c + 3); same order as the
   // split-image kernel: A pieces, dz reads, G rows, splits, G write, h loads, dz ring
-  // (par: c's parity, a compile-time constant after inlining — chunk c + 1's pieces sit in set
-  // (c + 1) % RING, refilled with chunk c + 1 + RING)
+  // (par: c modulo the loop's unroll, a compile-time constant after inlining — chunk c + 1's pieces
+  // sit in set (c + 1) % RING, refilled with chunk c + 1 + RING)
   auto unit = [&](int k, int c, int par) __attribute__((always_inline)) {
     constexpr int Z0 = 2 * NPA, G0 = Z0 + RP / 2, S0 = G0 + 2 * RP, P0 = S0 + RP / 2;
-    const int sa = RING == 1 ? 0 : (par ^ 1);
-    const int sg = RGN == 1 ? 0 : (par ^ 1);  // chunk c + 1's G rows
+    const int sa = RING == 1 ? 0 : (par + 1) % RING;
+    const int sg = RGN == 1 ? 0 : (par + 1) % RGN;  // chunk c + 1's G rows
+    const int sz = RZ == 1 ? 0 : (par + 2) % RZ;    // chunk c + 2's dz value
     if (k < Z0) {
       if (k & 1) {
-        if constexpr (ACT) load_a_at(sa, k >> 1, ab2);  // (RING = 1: chunk min(c + 2, clast))
+        if constexpr (ACT) load_a_at(sa, k >> 1, ab2);  // (chunk min(c + 1 + RING, clast))
         else load_a(sa, k >> 1, min(c + 1 + RING, clast));
       } else {
         put_a(sa, k >> 1, c + 1);
@@ -934,15 +962,15 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     } else if (k == P0) {
       g_put(c + 1);
     } else if (k == P0 + 1) {
-      if constexpr (ACT) load_g_at(sg, ab2);  // (RGN = 1: chunk min(c + 2, clast))
+      if constexpr (ACT) load_g_at(sg, ab2);  // (chunk min(c + 1 + RGN, clast))
       else load_g(sg, min(c + 1 + RGN, clast));
     } else if (k == P0 + 2) {
       if constexpr (ACT) {
-        put_zlh(c + 2, az2lo, az2hi, rz);
-        load_z_at(ab3);
+        put_zlh(c + 2, az2lo, az2hi, rz[sz]);
+        load_z_at(sz, ab3);  // (chunk min(c + 2 + RZ, clast))
       } else {
         put_z(c + 2);
-        load_z(min(c + 3, clast));
+        load_z(0, min(c + 3, clast));
       }
     }
   };
@@ -961,8 +989,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     if constexpr (ACT) {  // the list entries this chunk's staging units need, beside the fragment reads
       glo = az2lo;  // (chunk c + 1's, whose G rows this chunk's units form)
       zrange(c + 2, az2lo, az2hi);
-      ab2 = ldbase(min(c + 2, clast));
-      ab3 = ldbase(min(c + 3, clast));
+      ab2 = ldbase(min(c + 1 + RD, clast));
+      ab3 = ldbase(min(c + 2 + RD, clast));
     }
     f16x8 gf[3], af[2][2];  // G: hi', hi, lo; A: hi, lo
 #pragma unroll
@@ -1009,12 +1037,14 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     // strong-scaling shard, where a block walks only ~8 chunks)
 #pragma unroll
     for (int j = 0; j < NPA; ++j) load_a(0, j, 0);
-    if constexpr (RING == 2) {
 #pragma unroll
-      for (int j = 0; j < NPA; ++j) load_a(1, j, min(1, clast));
+    for (int s = 1; s < RING; ++s) {  // set s: chunk s
+#pragma unroll
+      for (int j = 0; j < NPA; ++j) load_a(s, j, min(s, clast));
     }
     load_g(0, 0);
-    if constexpr (RGN == 2) load_g(1, min(1, clast));
+#pragma unroll
+    for (int s = 1; s < RGN; ++s) load_g(s, min(s, clast));
     float* dzb = reinterpret_cast<float*>(&At[0][0]) + NW * 2 * 256;  // CSC: the block's dz rows
     if constexpr (CSC && !GF) {  // this block's dz[:, 0:ccols] (At is scratch until chunk 0's put)
       zm_fold = tn_csc_fold<NW>(a, mbeg, mend, reinterpret_cast<float*>(&At[0][0]) + wave * 2 * 256, dzb, lane, wave);
@@ -1032,7 +1062,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
       rz0 = a.dz[(uint32_t)((ldbase(0) + zr) * (int)a.lddz + zqc)];
       rz1 = a.dz[(uint32_t)((ldbase(min(1, clast)) + zr) * (int)a.lddz + zqc)];
     }
-    load_z(min(2, clast));
+#pragma unroll
+    for (int s = 0; s < RZ; ++s) load_z((2 + s) % RZ, min(2 + s, clast));  // chunk k in slot k % RZ
     put_zv(0, rz0);
     put_zv(1, rz1);
     scan_scale();     // (its barrier also publishes dzL)
@@ -1055,12 +1086,24 @@ __global__ __launch_bounds__(64 * NW) void gemm_tn_h2_kernel(TNArgs a) {
     for (int j = 0; j < NPA; ++j) load_a(0, j, min(RING, clast));  // set 0: chunk RING (1 or 2)
     load_g(0, min(RGN, clast));  // set 0: chunk RGN (1 or 2)
     __syncthreads();
-    for (int c = 0; c < nch; c += 2) {  // unrolled by 2: the ring's set indices are static
-      compute(c, std::integral_constant<int, 0>{});
-      __syncthreads();
-      if (c + 1 < nch) {
-        compute(c + 1, std::integral_constant<int, 1>{});
+    if constexpr (RD == 1) {
+      for (int c = 0; c < nch; c += 2) {  // unrolled by 2: the ring's set indices are static
+        compute(c, std::integral_constant<int, 0>{});
         __syncthreads();
+        if (c + 1 < nch) {
+          compute(c + 1, std::integral_constant<int, 1>{});
+          __syncthreads();
+        }
+      }
+    } else {
+      for (int c = 0; c < nch; c += RD) {  // unrolled by the ring depth, for the same reason
+        static_for<RD>([&](auto ic) __attribute__((always_inline)) {
+          constexpr int i = decltype(ic)::value;
+          if (c + i < nch) {  // (block-uniform)
+            compute(c + i, ic);
+            __syncthreads();
+          }
+        });
       }
     }
   }
@@ -1472,14 +1515,17 @@ bool tn_h2_ok(const TNArgs& a) {
 // 8 waves (two per SIMD, the k-tiles split between them): lab 102.3 -> 95.2 us on the headline
 // shape (profiles/r19_lab_h2.txt), the staging alone 93.4 — the kernel now runs at its stream
 // ks: split-K block pairs (gemm_tn_h2_kernel KS = 2; nblk = 2 x the row blocks; the dz form)
-void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks) {
+// act_split: the flag-driven form's column split (nblk = TN_ACT_SPLIT x the row blocks, loads
+// TN_ACT_RING chunks deep), or its first form, one block per row block and one chunk of loads
+void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks, bool act_split) {
   if (!a.dz) {  // the g form
     if (a.ap_ld == 176) gemm_tn_h2_kernel<6, false, 0, 8, true><<<nblk, 512, 0, st>>>(a);
     else gemm_tn_h2_kernel<11, false, 0, 8, true><<<nblk, 512, 0, st>>>(a);
     return;
   }
   if (a.dz_active) {  // (ABI 28) the flagged chunks only (the caller checked: no gout, no fold, not ks)
-    gemm_tn_h2_kernel<11, false, 0, 8, false, 1, false, true><<<nblk, 512, 0, st>>>(a);
+    if (act_split) gemm_tn_h2_kernel<11, false, 0, 8, false, TN_ACT_SPLIT, false, true, TN_ACT_RING><<<nblk, 512, 0, st>>>(a);
+    else gemm_tn_h2_kernel<11, false, 0, 8, false, 1, false, true><<<nblk, 512, 0, st>>>(a);
     return;
   }
   if (a.cptr) {  // (ABI 26) the CSC sum of u folded in (tn_h2_ok: no gout)

@@ -596,6 +596,16 @@ gnn_status gnn_gemm_tn_active_f32(const gnn_gemm_tn_params* p, const uint8_t* dz
 /* 1 when the flags pay at M rows: the dz-form row block is larger than the in-kernel CSC fold takes
  * (more than 448 rows a block, M > 114,688) — a rule of M alone, so every route to the TN agrees. */
 int gnn_gemm_tn_active_pays(int64_t M);
+/* The flag-driven TN's launch form: each row block runs as gnn_gemm_tn_active_split() blocks, one per
+ * contiguous range of 32-column k-tiles of the 336-wide image (11 tiles dealt as evenly as they go,
+ * the longer ranges first), every block walking the same chunk list with the same scale into its
+ * columns of the row block's one slab, with the loads of gnn_gemm_tn_active_ring() chunks in flight.
+ * Row blocks without a flagged chunk write one word and the reduce skips their slabs.  None of it
+ * changes a bit of the output.  Environment, read at every call (A/B): GNNMP_TN_ACTIVE_SPLIT=0 runs
+ * one block per row block with one chunk of loads in flight, GNNMP_TN_EMPTY_SKIP=0 writes and reads
+ * the zero slabs. */
+int gnn_gemm_tn_active_split(void);
+int gnn_gemm_tn_active_ring(void);
 /* The number nb of norm partials a call with sq_partial writes for an out of n_out floats (ABI 20). */
 gnn_status gnn_gemm_tn_sq_blocks(int64_t n_out, int32_t* nb);
 /* 1 when the call would read A from p->a_planes (the f32 A operands are then not needed), else 0.
