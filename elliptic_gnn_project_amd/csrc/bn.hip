@@ -343,12 +343,15 @@ extern "C" gnn_status gnn_bn_stats_f32(const float* z, int64_t ldz, int64_t N, i
                                        float eps, float momentum, float* mean, float* invstd, float* running_mean,
                                        float* running_var, int64_t* num_batches_tracked, void* workspace,
                                        size_t workspace_bytes, gnn_stream_t stream) {
-  if (N < 1 || C < 1 || C > 4096 || ldz < C || !z || !stats) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
+  if (N < 0 || C < 1 || C > 4096 || ldz < C || (N > 0 && !z) || !stats) return fail(GNN_ERR_INVALID_ARG, __func__, "bad args");
+  if (N == 0 && finalize) return fail(GNN_ERR_INVALID_ARG, __func__, "N = 0 has no batch mean to finalize");
   if (finalize && (!mean || !invstd || (running_mean && !running_var)))
     return fail(GNN_ERR_INVALID_ARG, __func__, "finalize needs mean / invstd (and running_var with running_mean)");
   if (!workspace || workspace_bytes < (size_t)kBnBlocks * 2 * (size_t)C * sizeof(double))
     return fail(GNN_ERR_WORKSPACE, __func__, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
+  // an empty shard of a process group: zero sums and n = 0 into the all-reduce (as the backward reduce)
+  if (N == 0) return hip_check(hipMemsetAsync(stats, 0, (2 * C + 1) * sizeof(double), st), __func__);
   BnArgs a{};
   a.z = z; a.ldz = ldz; a.N = N; a.C = (int32_t)C;
   const int64_t R = bn_rows_per_block(N, C);

@@ -75,6 +75,12 @@ def test_host_side_argument_validation(lib):
         _lib.check(lib.gnn_colsum_workspace_size(-1, 3, n), "colsum")
     p = _lib.GnnGemmNTParams()  # all zero: rejected as invalid shapes
     assert lib.gnn_gemm_nt_f32(p, None) == 1
+    # K12 statistics of an empty shard: finalize has no batch mean to form (pointers never dereferenced;
+    # finalize = 0 writes zero statistics, a device call: test_gpu_bn_geometry.py)
+    fake = 1 << 20
+    assert lib.gnn_bn_stats_f32(fake, 4, 0, 4, fake, 1, 1e-5, 0.1, fake, fake, None, None, None, fake, 1 << 20, None) == 1
+    assert b"N = 0" in lib.gnn_last_error()
+    assert lib.gnn_bn_stats_f32(fake, 4, -1, 4, fake, 0, 1e-5, 0.1, None, None, None, None, None, fake, 1 << 20, None) == 1
 
 
 def test_dropout_index_range_is_checked(lib):
