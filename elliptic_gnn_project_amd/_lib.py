@@ -227,6 +227,11 @@ FIT_THREADS = 1024  # GNN_FIT_THREADS
 CURVE_OUTPUTS = 8  # GNN_CURVE_OUTPUTS
 CALIB_MAX_BINS = 32  # GNN_CALIB_MAX_BINS
 
+# K19 (additive to ABI 32)
+REPORT_MAX_SEGMENTS = 2048  # GNN_REPORT_MAX_SEGMENTS
+REPORT_STATUS_K, JOIN_STATUS_DUPLICATE, JOIN_STATUS_NEGATIVE, JOIN_STATUS_MISMATCH = 8, 16, 32, 64
+ENSEMBLE_PROB, ENSEMBLE_LOGIT = 0, 1
+
 
 class GnnExplainStepParams(ctypes.Structure):
     """gnn_explain_step_params (ABI 31): one mask's fused GNNExplainer step (K16)."""
@@ -478,6 +483,16 @@ SIGNATURES = {
     "gnn_hub_rank": (ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_hub_ablate_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
     "gnn_hub_ablate": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_size, c_ptr]),
+    # K19 (additive to ABI 32)
+    "gnn_rank_hits_at_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_rank_hits_at": (
+        ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_segment_threshold_counts_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_segment_threshold_counts": (
+        ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, ctypes.c_double, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_id_join_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_id_join": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_ensemble_pair": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

@@ -1106,6 +1106,79 @@ gnn_status gnn_hub_ablate(const int64_t* edge_index, int64_t num_edges, const in
                           int64_t num_hubs, int64_t kept, int64_t* out, void* workspace,
                           size_t workspace_bytes, gnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* K19 run reports (additive to ABI 32: new symbols only, no struct touched): what the tools of the
+ *     reference's "Analysis" section need beyond K14 / K17 — src/analysis/workload_curves.py,
+ *     eval_by_time.py and evaluate_ensemble.py (calibration_plots.py reads K17's bins)          */
+/* ------------------------------------------------------------------------ */
+#define GNN_REPORT_MAX_SEGMENTS 2048     /* groups of gnn_segment_threshold_counts (one block's LDS histogram) */
+/* further bits of the device status word (GNN_RANK_STATUS_* above; the caller zeroes and reads it) */
+#define GNN_REPORT_STATUS_K 8            /* a ks[j] is below 1: its outputs are 0, 0, NaN */
+#define GNN_JOIN_STATUS_DUPLICATE 16     /* an id occurs twice in base_ids or in other_ids */
+#define GNN_JOIN_STATUS_NEGATIVE 32      /* an id is negative */
+#define GNN_JOIN_STATUS_MISMATCH 64      /* the two arrays do not hold the same set of ids */
+/* gnn_ensemble_pair's mode */
+#define GNN_ENSEMBLE_PROB 0
+#define GNN_ENSEMBLE_LOGIT 1
+
+/*
+ * gnn_rank_hits_at: for a ONE-segment plan (order, seg_ptr; m = seg_ptr[1] stays on the device),
+ * positive[n] indexed by element and ks[num_k] (DEVICE int64, each >= 1):
+ *   k_eff[j] = min(ks[j], m);   hits[j] = positives among plan positions 0 .. k_eff[j] - 1 (int64);
+ *   precision[j] = (double)hits[j] / (double)k_eff[j], NaN when m = 0.
+ * One inclusive scan of the labels in plan order and one gather: integer counts and one IEEE division,
+ * bitwise reproducible.  A ks[j] < 1 sets GNN_REPORT_STATUS_K and writes 0, 0, NaN.  num_k = 0 launches
+ * nothing.  INVALID_ARG before any launch: negative n or num_k, n >= INT32_MAX, num_segments != 1, a null
+ * buffer; WORKSPACE for a missing or short one.
+ */
+gnn_status gnn_rank_hits_at_workspace_size(int64_t n, size_t* bytes);
+gnn_status gnn_rank_hits_at(const int32_t* order, const int32_t* seg_ptr, const uint8_t* positive, int64_t n,
+                            int64_t num_segments, const int64_t* ks, int64_t num_k, int64_t* k_eff,
+                            int64_t* hits, double* precision, int32_t* status, void* workspace,
+                            size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * gnn_segment_threshold_counts: one pass over scores[n] (f32), positive[n], include[n] (NULL = all) and
+ * segment[n] (int32 in [0, S)), no sort and no plan: counts[S, 4] (int64) = per segment the TP, FP and FN
+ * of (double)score >= thr and the number of included elements.  An included element whose segment is
+ * outside [0, S) sets GNN_RANK_STATUS_SEGMENT and is skipped.  Integer sums (LDS atomics per block, the
+ * blocks' rows added in block order): the same bits whatever the order.  thr must be a float32 value, as
+ * for gnn_threshold_calibration.  S = 0 launches nothing.  INVALID_ARG before any launch: a negative
+ * size, S > GNN_REPORT_MAX_SEGMENTS, thr not a float32 value, a null buffer; WORKSPACE for a missing or
+ * short one.
+ */
+gnn_status gnn_segment_threshold_counts_workspace_size(int64_t n, int64_t num_segments, size_t* bytes);
+gnn_status gnn_segment_threshold_counts(const float* scores, const uint8_t* positive, const uint8_t* include,
+                                        const int32_t* segment, int64_t n, int64_t num_segments, double thr,
+                                        int64_t* counts, int32_t* status, void* workspace,
+                                        size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * gnn_id_join: perm[n] (int32) with other_ids[perm[i]] == base_ids[i] for two DEVICE int64 arrays that
+ * hold the same n distinct non-negative ids.  Two stable radix sorts of (id, position) pairs over all 64
+ * key bits, an element-wise comparison of the sorted keys and a scatter.  Status bits:
+ * GNN_JOIN_STATUS_DUPLICATE (adjacent equal sorted keys in either array), GNN_JOIN_STATUS_NEGATIVE,
+ * GNN_JOIN_STATUS_MISMATCH (sorted keys differ); perm is unspecified (but written inside [0, n)) when any
+ * is set.  n = 0 launches nothing.  INVALID_ARG before any launch: negative n, n >= INT32_MAX, a null
+ * buffer; WORKSPACE for a missing or short one.
+ */
+gnn_status gnn_id_join_workspace_size(int64_t n, size_t* bytes);
+gnn_status gnn_id_join(const int64_t* base_ids, const int64_t* other_ids, int64_t n, int32_t* perm,
+                       int32_t* status, void* workspace, size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * gnn_ensemble_pair: out[i] (f32) from x = a[perm_a[i]] (a[i] when perm_a is NULL) and y = b[i], both f32:
+ *   GNN_ENSEMBLE_PROB   0.5f * (x + y) in f32 (numpy's 0.5 * (pa + pb) on f32 scores, bit for bit);
+ *   GNN_ENSEMBLE_LOGIT  x, y clipped in f32 to [(float)1e-6, (float)(1 - 1e-6)], then in f64, every
+ *                       operation rounded once: r = sqrt(x y), q = sqrt((1 - x)(1 - y)),
+ *                       out = (float)(r / (r + q)) — the closed form of sigma((logit x + logit y) / 2).
+ * A NaN input sets GNN_RANK_STATUS_NAN, a perm_a[i] outside [0, n) GNN_RANK_STATUS_INDEX; both write NaN.
+ * Element-wise: no workspace.  n = 0 launches nothing.  INVALID_ARG before any launch: negative n,
+ * n >= INT32_MAX, another mode, a null buffer.
+ */
+gnn_status gnn_ensemble_pair(const float* a, const float* b, const int32_t* perm_a, int64_t n, int32_t mode,
+                             float* out, int32_t* status, gnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
