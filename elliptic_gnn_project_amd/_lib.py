@@ -232,6 +232,13 @@ REPORT_MAX_SEGMENTS = 2048  # GNN_REPORT_MAX_SEGMENTS
 REPORT_STATUS_K, JOIN_STATUS_DUPLICATE, JOIN_STATUS_NEGATIVE, JOIN_STATUS_MISMATCH = 8, 16, 32, 64
 ENSEMBLE_PROB, ENSEMBLE_LOGIT = 0, 1
 
+# K20 (additive to ABI 32)
+LOGREG_MAX_D = 255  # GNN_LOGREG_MAX_D
+LOGREG_ROWS = 128  # GNN_LOGREG_ROWS
+LOGREG_REDUCE_UNROLL = 4  # GNN_LOGREG_REDUCE_UNROLL
+ISOTONIC_CHUNK = 128  # GNN_ISOTONIC_CHUNK
+BASELINE_STATUS_ROW, BASELINE_STATUS_NAN = 1, 2
+
 
 class GnnExplainStepParams(ctypes.Structure):
     """gnn_explain_step_params (ABI 31): one mask's fused GNNExplainer step (K16)."""
@@ -493,6 +500,21 @@ SIGNATURES = {
     "gnn_id_join_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
     "gnn_id_join": (ctypes.c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_ensemble_pair": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr]),
+    # K20 (additive to ABI 32)
+    "gnn_column_moments_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_column_moments": (
+        ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_logreg_eval_workspace_size": (ctypes.c_int, [c_i64, c_i64, ctypes.POINTER(c_size)]),
+    "gnn_logreg_eval": (
+        ctypes.c_int,
+        [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_double, ctypes.c_double,
+         ctypes.c_double, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_logreg_predict": (
+        ctypes.c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "gnn_isotonic_fit_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
+    "gnn_isotonic_fit": (
+        ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_isotonic_apply": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

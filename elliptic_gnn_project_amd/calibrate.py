@@ -27,6 +27,26 @@ softplus(-t) = max(-t, 0) + log1p(e).  The rules, in order:
 
 T = float32(1 / beta).  An included row with a label outside {0, 1} or a NaN / infinite logit is
 skipped and reported: a ValueError here.  Other widths than two classes keep the LBFGS path.
+
+The score calibrators of src/utils/calibrate.py:32-47 (``fit_isotonic``, ``fit_platt``,
+``apply_calibrator``; libgnnmp K20, csrc/baseline.hip, for CUDA scores and numpy for the rest), defined on
+f32 scores and positives ``y == 1`` over the included elements (``mask``, default ``y >= 0``):
+
+* isotonic (IsotonicRegression(out_of_bounds="clip")): the points are the tie groups of bit-equal scores
+  (-0.0 == +0.0) in ascending order — the groups of the rank plan — each with integers P (positives) and
+  W (elements).  PAVA pools adjacent blocks a (left), b while P_a W_b >= P_b W_a (int64; equal means pool,
+  as in sklearn); a block's value is the one f64 division P / W, so the solution is integer-exact and the
+  same bits however the work is chunked.  Trim: the first and the last point stay, an interior point k
+  stays iff y_k != y_{k-1} or y_k != y_{k+1}.  Apply (scipy's linear interp1d as sklearn calls it), in f64
+  with each operation rounded once: x clipped to [x_0, x_{K-1}], i = clip(searchsorted_left(xs, x), 1,
+  K - 1), slope = (y_i - y_{i-1}) / (x_i - x_{i-1}), out = slope (x - x_{i-1}) + y_{i-1}; K = 1 gives the
+  constant.  sklearn first merges scores closer than the dtype's resolution (1e-10 apart for f64 input);
+  this does not.
+* Platt (LogisticRegression on the score): logreg.fit on the one raw column — the f32 score upcast, no
+  standardising, C = 1, no class weight: the minimiser of sklearn's objective; apply = sigma(w s + b).
+
+A NaN score among the included elements is a ValueError; an empty fit set gives the identity and status
+EMPTY.  The calibrated score is the f64 value rounded once to f32 (the project's score dtype).
 """
 from __future__ import annotations
 
@@ -189,3 +209,182 @@ def fit_temperature(logits: torch.Tensor, y: torch.Tensor, mask: Optional[torch.
         details.update(beta=got[0], f=got[1], g=got[2], iterations=int(got[3]), status=int(got[4]))
     check_status(int(got[4]))
     return T
+
+
+# ----------------------------------------------------------------------------- score calibrators (K20)
+class Calibrator:
+    """kind "identity", "isotonic" (thresholds xs, ys: f64) or "platt" (w, b); ``status`` a FIT_STATUS_* word."""
+
+    def __init__(self, kind: str, xs=None, ys=None, w: float = 1.0, b: float = 0.0, status: int = 0, model=None):
+        self.kind, self.status, self.model = kind, int(status), model
+        self.xs = np.zeros(0) if xs is None else np.asarray(xs, dtype=np.float64)
+        self.ys = np.zeros(0) if ys is None else np.asarray(ys, dtype=np.float64)
+        self.w, self.b = float(w), float(b)
+
+
+def _np(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _is_device(*ts) -> bool:
+    return any(isinstance(t, torch.Tensor) and t.is_cuda for t in ts)
+
+
+def _host_fit_inputs(scores, y, mask):
+    s = np.asarray(_np(scores), dtype=np.float32).reshape(-1)
+    yy = _np(y).reshape(-1)
+    if yy.size != s.size or (mask is not None and _np(mask).size != s.size):
+        raise ValueError("calibrate: y / mask do not match the scores")
+    inc = (yy >= 0) if mask is None else _np(mask).reshape(-1).astype(bool)
+    if np.isnan(s[inc]).any():
+        raise ValueError("calibrate: NaN score among the included elements")
+    return s, yy == 1, inc
+
+
+def host_isotonic_fit(scores: np.ndarray, positive: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(xs, ys) of the module docstring for f32 scores (no NaN) and bool positives, at least one element."""
+    s = np.asarray(scores, dtype=np.float32) + np.float32(0.0)  # -0.0 -> +0.0
+    x, inv = np.unique(s, return_inverse=True)
+    W = np.bincount(inv, minlength=x.size).astype(np.int64)
+    P = np.bincount(inv, weights=np.asarray(positive, dtype=np.float64), minlength=x.size).astype(np.int64)
+    bp, bw, bn = [], [], []  # the stack of blocks: positives, elements, points
+    for p, w in zip(P.tolist(), W.tolist()):
+        n = 1
+        while bp and bp[-1] * w >= p * bw[-1]:
+            p, w, n = p + bp.pop(), w + bw.pop(), n + bn.pop()
+        bp.append(p)
+        bw.append(w)
+        bn.append(n)
+    val = np.asarray(bp, dtype=np.float64) / np.asarray(bw, dtype=np.float64)
+    yv = np.repeat(val, bn)
+    keep = np.ones(x.size, dtype=bool)
+    if x.size > 2:
+        keep[1:-1] = (yv[1:-1] != yv[:-2]) | (yv[1:-1] != yv[2:])
+    return x[keep].astype(np.float64), yv[keep]
+
+
+def host_isotonic_apply(xs: np.ndarray, ys: np.ndarray, q: np.ndarray) -> np.ndarray:
+    x = np.asarray(q, dtype=np.float32).astype(np.float64)
+    K = int(xs.size)
+    if K == 0:
+        return x
+    if K == 1:
+        return np.where(np.isnan(x), np.nan, ys[0])
+    xc = np.clip(x, xs[0], xs[-1])
+    i = np.clip(np.searchsorted(xs, xc, side="left"), 1, K - 1)
+    slope = (ys[i] - ys[i - 1]) / (xs[i] - xs[i - 1])
+    return slope * (xc - xs[i - 1]) + ys[i - 1]
+
+
+_ISO_WS: Dict[tuple, torch.Tensor] = {}
+
+
+def _iso_workspace(device: torch.device, n: int) -> torch.Tensor:
+    key = (device.index if device.index is not None else torch.cuda.current_device(), n)
+    ws = _ISO_WS.get(key)
+    if ws is None:
+        b = _lib.c_size(0)
+        _lib.check(_lib.load().gnn_isotonic_fit_workspace_size(n, ctypes.byref(b)), "gnn_isotonic_fit_workspace_size")
+        ws = _ISO_WS[key] = torch.empty(b.value, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _device_isotonic_fit(scores, y, mask) -> Calibrator:
+    from . import rank_metrics
+
+    s, yy, inc = rank_metrics._device_inputs(scores, y, mask)
+    s = s.detach().to(torch.float32).contiguous()
+    n, dev = int(s.numel()), s.device
+    if n == 0:
+        return Calibrator("identity", status=_lib.FIT_STATUS_EMPTY)
+    buf = rank_metrics._buffers(dev, n, 1, "iso")
+    xs = torch.empty(n, dtype=torch.float64, device=dev)
+    ys = torch.empty(n, dtype=torch.float64, device=dev)
+    K = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _iso_workspace(dev, n)
+    with torch.cuda.device(dev):
+        rank_metrics._build_plan(buf, s, inc, None)
+        _lib.call("gnn_isotonic_fit", _lib.ptr(s), _lib.ptr(buf.order), _lib.ptr(buf.flags), _lib.ptr(buf.seg_ptr),
+                  _lib.ptr(rank_metrics._u8(yy == 1)), n, 1, _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(K), _lib.ptr(ws),
+                  ws.numel(), _lib.stream_handle(dev))
+    got = torch.cat([K, buf.status.to(torch.int64)]).cpu()  # the one host read
+    if int(got[1]) & _lib.RANK_STATUS_NAN:
+        raise ValueError("calibrate: NaN score among the included elements")
+    k = int(got[0])
+    if k == 0:
+        return Calibrator("identity", status=_lib.FIT_STATUS_EMPTY)
+    return Calibrator("isotonic", xs[:k].cpu().numpy(), ys[:k].cpu().numpy())
+
+
+def fit_isotonic(scores, y, mask=None) -> Calibrator:
+    """The isotonic calibrator of the included elements (module docstring); CUDA tensors take the device
+    path (one rank plan, gnn_isotonic_fit), arrays and host tensors the numpy mirror."""
+    if _is_device(scores, y, mask):
+        return _device_isotonic_fit(scores, y, mask)
+    s, pos, inc = _host_fit_inputs(scores, y, mask)
+    if not inc.any():
+        return Calibrator("identity", status=_lib.FIT_STATUS_EMPTY)
+    return Calibrator("isotonic", *host_isotonic_fit(s[inc], pos[inc]))
+
+
+def fit_platt(scores, y, mask=None) -> Calibrator:
+    """The Platt calibrator: logreg.fit on the one raw score column, C = 1, no class weight."""
+    from . import logreg
+
+    if _is_device(scores, y, mask):
+        from . import rank_metrics
+
+        s, yy, inc = rank_metrics._device_inputs(scores, y, mask)
+        s = s.detach().to(torch.float32).contiguous()
+        rows = torch.nonzero(inc).flatten()
+        if bool(torch.isnan(s[rows]).any()):
+            raise ValueError("calibrate: NaN score among the included elements")
+    else:
+        s, pos, incn = _host_fit_inputs(scores, y, mask)
+        yy, rows = pos.astype(np.int64), np.nonzero(incn)[0]
+    if int(rows.shape[0]) == 0:
+        return Calibrator("identity", status=_lib.FIT_STATUS_EMPTY)
+    m = logreg.fit(s.reshape(-1, 1), yy, rows=rows, C=1.0, class_weight=None, max_iter=MAX_IT, standardize=False)
+    status = _lib.FIT_STATUS_MAXIT if m.status & logreg.STATUS_MAXIT else 0
+    return Calibrator("platt", w=float(m.w[0]), b=m.b, status=status, model=m)
+
+
+def apply_calibrator(cal: Calibrator, scores, dtype=np.float32):
+    """The calibrated scores: a tensor on the scores' device for CUDA scores, else a numpy array, as f32
+    (default; the f64 value rounded once) or f64.  A NaN score is a ValueError."""
+    f64 = np.dtype(dtype) == np.float64
+    if _is_device(scores):
+        s = scores.detach().to(torch.float32).contiguous().reshape(-1)
+        n, dev = int(s.numel()), s.device
+        if cal.kind == "identity" or n == 0:
+            return s.double() if f64 else s.clone()
+        if cal.kind == "platt":
+            from . import logreg
+
+            if bool(torch.isnan(s).any()):
+                raise ValueError("calibrate: NaN score")
+            return logreg.predict_proba(cal.model, s.reshape(-1, 1), None, np.float64 if f64 else np.float32)
+        xs = torch.from_numpy(cal.xs).to(dev)
+        ys = torch.from_numpy(cal.ys).to(dev)
+        K = torch.tensor([cal.xs.size], dtype=torch.int64, device=dev)
+        o64 = torch.empty(n, dtype=torch.float64, device=dev)
+        o32 = torch.empty(n, dtype=torch.float32, device=dev)
+        st = torch.zeros(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.call("gnn_isotonic_apply", _lib.ptr(xs), _lib.ptr(ys), _lib.ptr(K), _lib.ptr(s), n, _lib.ptr(o64),
+                      _lib.ptr(o32), _lib.ptr(st), _lib.stream_handle(dev))
+        if int(st) & _lib.BASELINE_STATUS_NAN:
+            raise ValueError("calibrate: NaN score")
+        return o64 if f64 else o32
+    s = np.asarray(_np(scores), dtype=np.float32).reshape(-1)
+    if np.isnan(s).any():
+        raise ValueError("calibrate: NaN score")
+    if cal.kind == "identity":
+        out = s.astype(np.float64)
+    elif cal.kind == "platt":
+        from . import logreg
+
+        out = logreg.host_predict(s.reshape(-1, 1), np.arange(s.size), cal.model)
+    else:
+        out = host_isotonic_apply(cal.xs, cal.ys, s)
+    return out if f64 else out.astype(np.float32)

@@ -1179,6 +1179,88 @@ gnn_status gnn_id_join(const int64_t* base_ids, const int64_t* other_ids, int64_
 gnn_status gnn_ensemble_pair(const float* a, const float* b, const int32_t* perm_a, int64_t n, int32_t mode,
                              float* out, int32_t* status, gnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* K20 feature-only baseline (additive to ABI 32: new symbols only, no struct touched): the logistic
+ *     regression of src/train_baselines.py and the isotonic / Platt calibrators of
+ *     src/utils/calibrate.py:32-47, as logreg.py and calibrate.py define them                       */
+/* ------------------------------------------------------------------------ */
+#define GNN_LOGREG_MAX_D 255             /* feature columns of a fit (D + 1 <= 256: the H tiles of one block) */
+#define GNN_LOGREG_ROWS 128              /* listed rows per block: one partial (F, g, H) slab each */
+#define GNN_LOGREG_REDUCE_UNROLL 4       /* slabs a reduce thread loads per step (the adds stay one chain) */
+#define GNN_ISOTONIC_CHUNK 128           /* tie groups per independent PAVA chunk */
+/* bits of the K20 calls' device status word (the caller zeroes and reads it) */
+#define GNN_BASELINE_STATUS_ROW 1        /* a listed row is outside [0, num_rows): it was skipped */
+#define GNN_BASELINE_STATUS_NAN 2        /* gnn_isotonic_apply: a query is NaN (NaN is written) */
+
+/*
+ * Common to the three row-list calls: x[num_rows, D] f32 with row stride ld >= D, rows[n] (int32; NULL =
+ * the rows 0 .. n-1) the selected rows in order, 1 <= D <= GNN_LOGREG_MAX_D.  mu[D], sd[D] (f64; both
+ * NULL = raw columns) standardise on the fly: z_ij = ((double)x_ij - mu_j) / sd_j, never stored.  n = 0
+ * launches nothing.  INVALID_ARG before any launch: a negative size, D outside its range, ld < D, n or
+ * num_rows >= INT32_MAX, a null buffer, one of mu / sd without the other; WORKSPACE for a missing or short
+ * one.  A listed row outside [0, num_rows) sets GNN_BASELINE_STATUS_ROW and is skipped.
+ *
+ * gnn_column_moments: mu_j = sum x_ij / n, var_j = sum (x_ij - mu_j)^2 / n (two passes, f64),
+ * sd_j = sqrt(var_j), 1 where var_j == 0.  Sums in row order inside a block of GNN_LOGREG_ROWS rows, the
+ * blocks in block order: bitwise reproducible.
+ */
+gnn_status gnn_column_moments_workspace_size(int64_t n, int64_t D, size_t* bytes);
+gnn_status gnn_column_moments(const float* x, int64_t ld, int64_t num_rows, const int32_t* rows, int64_t n,
+                              int64_t D, double* mu, double* sd, int32_t* status, void* workspace,
+                              size_t workspace_bytes, gnn_stream_t stream);
+
+/*
+ * gnn_logreg_eval: at theta[D + 1] = (w, b) (f64, device), with t_i = z_i.w + b, y[num_rows] bytes indexed
+ * by row (non-zero = positive) and s_i = w1 for a positive row, w0 otherwise:
+ *   F = C sum_i s_i (softplus(t_i) - y_i t_i) + 1/2 |w|^2                       (the intercept is free)
+ *   g[D + 1] = C A^T r + (w, 0),  r_i = s_i (sigma(t_i) - y_i)                  A = [Z | 1]
+ *   H[D + 1, D + 1] = C A^T S A + diag(1, .., 1, 0),  S_i = s_i sigma(t_i) sigma(-t_i)
+ * all f64, sigma and softplus through exp(-|t|).  value_only != 0 writes F alone (g, H may be NULL).
+ * Each block of GNN_LOGREG_ROWS rows writes one partial slab (one triangle of H); a second launch adds
+ * the slabs in order and mirrors the triangle: H is bitwise symmetric and two runs give the same bits.
+ * No atomics on floats.  Also INVALID_ARG: C not positive and finite, a negative or non-finite weight.
+ */
+gnn_status gnn_logreg_eval_workspace_size(int64_t n, int64_t D, size_t* bytes);
+gnn_status gnn_logreg_eval(const float* x, int64_t ld, int64_t num_rows, const int32_t* rows, int64_t n,
+                           int64_t D, const uint8_t* y, const double* mu, const double* sd, double w0,
+                           double w1, double C, const double* theta, int32_t value_only, double* F, double* g,
+                           double* H, int32_t* status, void* workspace, size_t workspace_bytes,
+                           gnn_stream_t stream);
+
+/* gnn_logreg_predict: p[k] = sigma(z_k.w + b) of listed row k, as f64 (p64) and / or f32 (p32); a row
+ * outside x writes NaN.  No workspace. */
+gnn_status gnn_logreg_predict(const float* x, int64_t ld, int64_t num_rows, const int32_t* rows, int64_t n,
+                              int64_t D, const double* mu, const double* sd, const double* theta, double* p64,
+                              float* p32, int32_t* status, gnn_stream_t stream);
+
+/*
+ * gnn_isotonic_fit: the isotonic regression (sklearn's IsotonicRegression(out_of_bounds="clip") thresholds)
+ * of positive[] on scores[] over the included elements of a ONE-segment rank plan of those scores
+ * (gnn_rank_plan_build: order, flags, seg_ptr).  The points are the plan's tie groups in ascending score
+ * order, each with integers P (positives) and W (elements); PAVA pools adjacent blocks a, b while
+ * P_a W_b >= P_b W_a (int64), a block's value is the f64 division P / W, and of the interior points only
+ * those whose value differs from a neighbour's are kept.  xs[K], ys[K] (f64, room for n each) and *K
+ * (device int64) are written; no included element gives K = 0.  Integer-exact: the same bits whatever the
+ * chunking (GNN_ISOTONIC_CHUNK groups per independent chunk, then pairwise merges that pool outward from
+ * each seam).  n = 0 launches nothing.  INVALID_ARG before any launch: negative n, n >= INT32_MAX,
+ * num_segments != 1, a null buffer; WORKSPACE for a missing or short one.
+ */
+gnn_status gnn_isotonic_fit_workspace_size(int64_t n, size_t* bytes);
+gnn_status gnn_isotonic_fit(const float* scores, const int32_t* order, const uint8_t* flags,
+                            const int32_t* seg_ptr, const uint8_t* positive, int64_t n, int64_t num_segments,
+                            double* xs, double* ys, int64_t* K, void* workspace, size_t workspace_bytes,
+                            gnn_stream_t stream);
+
+/*
+ * gnn_isotonic_apply: out[i] for the f32 queries, in f64 with every operation rounded once (scipy's linear
+ * interp1d as sklearn calls it): x clipped to [xs[0], xs[K-1]], j = clip(lower_bound(xs, x), 1, K - 1),
+ * slope = (ys[j] - ys[j-1]) / (xs[j] - xs[j-1]), out = slope (x - xs[j-1]) + ys[j-1]; K = 1 gives ys[0],
+ * K = 0 the query itself.  out64 and / or out32 = (float)out.  A NaN query sets GNN_BASELINE_STATUS_NAN
+ * and writes NaN.  INVALID_ARG before any launch: negative n, n >= INT32_MAX, a null buffer.
+ */
+gnn_status gnn_isotonic_apply(const double* xs, const double* ys, const int64_t* K, const float* queries,
+                              int64_t n, double* out64, float* out32, int32_t* status, gnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
