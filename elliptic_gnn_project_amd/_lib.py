@@ -189,6 +189,7 @@ class GnnGatFwdParams(ctypes.Structure):
 
 
 ADAM_MAX_TENSORS = 24
+ADAM_SELF_MAX = 1 << 15  # gradients of at most this many elements run gnn_clip_adam_f32's one-launch form
 
 
 class GnnAdamTensor(ctypes.Structure):
@@ -418,6 +419,8 @@ SIGNATURES = {
          c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_size, c_ptr],
     ),
     "gnn_clip_adam_f32": (ctypes.c_int, [ctypes.POINTER(GnnAdamGroup), c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "gnn_clip_adam_prep_f32": (ctypes.c_int, [ctypes.POINTER(GnnAdamGroup), c_ptr, c_ptr, c_ptr, c_size,
+                                              ctypes.POINTER(GnnGemmNTParams), c_i32, c_ptr]),
     "gnn_bn_workspace_size": (ctypes.c_int, [c_i64, ctypes.POINTER(c_size)]),
     "gnn_bn_stats_f32": (
         ctypes.c_int,

@@ -325,25 +325,16 @@ __device__ __forceinline__ float h2_col_exp2(float m) {  // 2^e with m · 2^-e i
   frexpf(m, &E);  // m in [2^(E-1), 2^E)
   return ldexpf(1.0f, E - 4);
 }
-template <int NTH>
-__device__ __forceinline__ void ws_prep_h2_cols(const H2Prep& a, int blk) {
-  constexpr int NW = NTH / 64;
+// The part behind a wave's loads, shared with the optimizer's riding form (train_ops.hip
+// clip_adam_kernel: the wave then holds the weights it has just updated): v[i] / v[6 + i] are
+// elements lane + 64 i of row n of w1 / w2 (whatever lies past k1 / k2, or in a column past Nc, is
+// masked here).  NW: the block's waves (wave threadIdx.x / 64 owns one LDS row); no block barrier.
+template <int NW>
+__device__ __forceinline__ void ws_prep_h2_finish(const H2Prep& a, int n, const float (&v)[12]) {
   constexpr int ROW = 16 * 24 + 4;                 // an image row (<= 384 columns) per wave
   __shared__ float wrow[NW][ROW];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n = blk * NW + wave;                   // this wave's column
-  if (n >= BN) return;                             // (wave-uniform; no block barrier below)
   const bool live = n < a.Nc;
-  const int nc = live ? n : 0;
-  const int k1m = a.k1 - 1, k2m = a.k2 > 0 ? a.k2 - 1 : 0;
-  const float* w1 = a.w1 + (int64_t)nc * a.ldw1;
-  const float* w2 = (a.w2 ? a.w2 : a.w1) + (int64_t)nc * (a.w2 ? a.ldw2 : a.ldw1);
-  float v[12];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    v[i] = w1[min(lane + 64 * i, k1m)];
-    v[6 + i] = w2[min(lane + 64 * i, k2m)];
-  }
   float* row = wrow[wave];
   const int ncols = 16 * a.blocks;
   for (int kk = lane; kk < ncols; kk += 64) row[kk] = 0.f;
@@ -381,6 +372,24 @@ __device__ __forceinline__ void ws_prep_h2_cols(const H2Prep& a, int blk) {
     a.img[((int64_t)s * 3 + 1) * 256 + slot] = make_uint4(hw[0], hw[1], hw[2], hw[3]);
     a.img[((int64_t)s * 3 + 2) * 256 + slot] = make_uint4(lw[0], lw[1], lw[2], lw[3]);
   }
+}
+template <int NTH>
+__device__ __forceinline__ void ws_prep_h2_cols(const H2Prep& a, int blk) {
+  constexpr int NW = NTH / 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n = blk * NW + wave;                   // this wave's column
+  if (n >= BN) return;                             // (wave-uniform; no block barrier below)
+  const int nc = n < a.Nc ? n : 0;
+  const int k1m = a.k1 - 1, k2m = a.k2 > 0 ? a.k2 - 1 : 0;
+  const float* w1 = a.w1 + (int64_t)nc * a.ldw1;
+  const float* w2 = (a.w2 ? a.w2 : a.w1) + (int64_t)nc * (a.w2 ? a.ldw2 : a.ldw1);
+  float v[12];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    v[i] = w1[min(lane + 64 * i, k1m)];
+    v[6 + i] = w2[min(lane + 64 * i, k2m)];
+  }
+  ws_prep_h2_finish<NW>(a, n, v);
 }
 constexpr int WS_PREP_THREADS = 1024;
 

@@ -6,8 +6,10 @@
 // Reductions are fixed-order (block partials summed in index order): bitwise reproducible.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "common.hpp"
+#include "gemm_common.hpp"
 
 namespace gnnmp {
 namespace {
@@ -155,6 +157,36 @@ __device__ __forceinline__ void finish_loss(const LossFinish& lf, float* sh) {
   if (threadIdx.x == 0) lf.out[0] = tl * lf.scale;
 }
 
+// One element's clip + Adam update (clip_adam_kernel below; its flat and row-owner paths both call
+// it): g is the gradient scaled by the clip coefficient, as written back to .grad
+struct AdamCoef { float coef, neg_step, bc2s, b2, omb1, omb2, epsf, wdf; };
+struct AdamElem { float g, m, v, p; };
+__device__ __forceinline__ AdamElem adam_element(const AdamCoef& c, float g0, float p0, float m0, float v0) {
+  AdamElem r;
+  float g = g0 * c.coef;
+  r.g = g;  // clip_grad_norm_ scales .grad in place
+  if (c.wdf != 0.f) g = g + c.wdf * p0;  // Adam (not AdamW) weight decay: grad.add(param, alpha=wd)
+  r.m = fmaf(c.omb1, g - m0, m0);  // exp_avg.lerp_(grad, 1 - beta1)
+  r.v = v0 * c.b2 + c.omb2 * g * g;
+  r.p = p0 + c.neg_step * (r.m / (sqrtf(r.v) / c.bc2s + c.epsf));
+  return r;
+}
+
+// The half-pair NTs whose B images ride in the optimizer's launch (gnn_clip_adam_prep_f32): the
+// Linear weights behind hp.w1 / hp.w2 are members of the Adam group, rows contiguous (ldw = k), and
+// are left out of the flat table: BN / 4 extra blocks per NT own them by rows, one wave per output
+// column n = row n of both (ws_prep_h2_cols' layout), and build column n of the image from the
+// updated values they hold.
+constexpr int kAdamMaxPrep = 4;          // (SAGE-ResBN would register four)
+constexpr int kAdamPrepBlocks = BN / 4;  // per NT: 4 waves of kAdamThreads, one column each
+struct AdamPrepNT {
+  H2Prep hp;
+  float *g1, *m1, *v1;  // .grad and moments of hp.w1 [Nc, k1]
+  float *g2, *m2, *v2;  // of hp.w2 [Nc, k2]; null when k2 = 0
+};
+struct AdamPrepList { int32_t n; AdamPrepNT nt[kAdamMaxPrep]; };
+struct AdamNoPrep {};
+
 __global__ __launch_bounds__(kAdamThreads) void grad_sq_kernel(AdamTable tb, float* __restrict__ partial,
                                                                 const float* __restrict__ step, LossFinish lf) {
   __shared__ float sh[kAdamThreads / 64];
@@ -214,7 +246,13 @@ constexpr int kSelfThreads = 1024;
 // vs 8.0 + 7.7 — the per-thread Σ passes grow with the count: profiles/r51_adam_one_launch.txt)
 constexpr int64_t kSelfMax = 1 << 15;
 static_assert(kSelfMax / 64 <= 4 * kSelfThreads, "a SELF block's Adam slice is one pass, loaded before the norm");
-template <int NTH = kAdamThreads, bool SELF = false>
+// PREP (not SELF): blocks own0 = kAdamBlocks (+ 1 with a loss block) .. own0 + pl.n·kAdamPrepBlocks - 1
+// own the rows of pl's weights (AdamPrepList above).  They form coef / skip from the same partials
+// by the same code as the flat blocks, load p, g, m and v of their rows before the reduction and
+// before any store, update through adam_element and then write their image columns; under a
+// skipped step (skip_nonfinite) they store no update and build the image of the unchanged weights.
+// No block waits for another.
+template <int NTH = kAdamThreads, bool SELF = false, bool PREP = false>
 __global__ __launch_bounds__(NTH) void clip_adam_kernel(AdamTable tb, const float* __restrict__ partial,
                                                         int nblk, int nf_off, int step_off,
                                                         float* __restrict__ step,
@@ -222,7 +260,9 @@ __global__ __launch_bounds__(NTH) void clip_adam_kernel(AdamTable tb, const floa
                                                         double beta2, double eps, double wd,
                                                         float* __restrict__ norm_out, int skip_nonfinite,
                                                         int64_t* __restrict__ bump, LossFinish lf,
-                                                        unsigned* __restrict__ done = nullptr) {
+                                                        unsigned* __restrict__ done = nullptr,
+                                                        std::conditional_t<PREP, AdamPrepList, AdamNoPrep> pl = {}) {
+  static_assert(!(PREP && SELF) && (!PREP || NTH == kAdamThreads), "the riding prep: the partials forms, 4 waves");
   __shared__ float coef_sh, snap_sh;
   __shared__ int skip_sh, last_sh;
   __shared__ float red_sh[2][NTH / 64];
@@ -256,6 +296,37 @@ __global__ __launch_bounds__(NTH) void clip_adam_kernel(AdamTable tb, const floa
     }
   };
   if (has) load_pass(e0 + threadIdx.x);
+  // a row-owner block (block-uniform; it has no flat slice: e0 >= total): wave w's column and its
+  // 6 + 6 elements per lane of p, g, m, v, indices clamped into the row
+  bool owner = false;
+  int on = 0, oi[12];
+  float og[12], op[12], om[12], ov[12];
+  if constexpr (PREP) {
+    const int own0 = kAdamBlocks + (lf.partial ? 1 : 0);
+    owner = (int)blockIdx.x >= own0;
+    if (owner) {
+      const int ob = (int)blockIdx.x - own0;
+      const AdamPrepNT& q = pl.nt[ob / kAdamPrepBlocks];
+      const int lane = threadIdx.x & 63;
+      on = (ob % kAdamPrepBlocks) * (NTH / 64) + (threadIdx.x >> 6);
+      const int nc = on < q.hp.Nc ? on : 0;
+      const int k1m = q.hp.k1 - 1, k2m = q.hp.k2 > 0 ? q.hp.k2 - 1 : 0;
+      const bool two = q.hp.w2 != nullptr;
+      float* p1 = const_cast<float*>(q.hp.w1);
+      float* p2 = two ? const_cast<float*>(q.hp.w2) : p1;
+      const float *g2 = two ? q.g2 : q.g1, *m2 = two ? q.m2 : q.m1, *v2 = two ? q.v2 : q.v1;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        oi[i] = nc * q.hp.k1 + min(lane + 64 * i, k1m);
+        oi[6 + i] = two ? nc * q.hp.k2 + min(lane + 64 * i, k2m) : 0;
+      }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {  // every load issued first
+        og[i] = q.g1[oi[i]]; op[i] = p1[oi[i]]; om[i] = q.m1[oi[i]]; ov[i] = q.v1[oi[i]];
+        og[6 + i] = g2[oi[6 + i]]; op[6 + i] = p2[oi[6 + i]]; om[6 + i] = m2[oi[6 + i]]; ov[6 + i] = v2[oi[6 + i]];
+      }
+    }
+  }
   {
     float tot = 0.f, nf = 0.f;
     if constexpr (SELF) {  // Σg² over every gradient, this block's own fixed order
@@ -345,7 +416,8 @@ __global__ __launch_bounds__(NTH) void clip_adam_kernel(AdamTable tb, const floa
     }
   }
   __syncthreads();
-  if (skip_sh) return;  // block-uniform
+  const bool skip = skip_sh;     // block-uniform
+  if (skip && !owner) return;    // (an owner block still builds its image)
   if constexpr (SELF) {
     // clip_grad_norm_'s in-place scaling of .grad: by the last block alone, once every block has
     // summed the gradients (a block writing its own slice earlier would change what a slower block
@@ -372,21 +444,40 @@ __global__ __launch_bounds__(NTH) void clip_adam_kernel(AdamTable tb, const floa
   const double bc1 = 1.0 - pow(beta1, t), bc2 = 1.0 - pow(beta2, t);
   const float neg_step = (float)(-lr / bc1), bc2s = (float)sqrt(bc2);
   const float b2 = (float)beta2, omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-  const float epsf = (float)eps, wdf = (float)wd;
+  const AdamCoef ac{coef, neg_step, bc2s, b2, omb1, omb2, (float)eps, (float)wd};
   for (int64_t e = e0 + threadIdx.x; has && e < e1; e += kAdamUnroll * NTH) {
     if (e != e0 + threadIdx.x) load_pass(e);  // (the first pass was loaded before the reduction)
 #pragma unroll
     for (int u = 0; u < kAdamUnroll; ++u) {
       if (!ok[u]) continue;
-      float g = g0[u] * coef;
-      if constexpr (!SELF) L.g[j[u]][i[u]] = g;  // clip_grad_norm_ scales .grad in place (SELF: above)
-      if (wdf != 0.f) g = g + wdf * p[u];  // Adam (not AdamW) weight decay: grad.add(param, alpha=wd)
-      const float m = fmaf(omb1, g - m0[u], m0[u]);  // exp_avg.lerp_(grad, 1 - beta1)
-      const float v = v0[u] * b2 + omb2 * g * g;
-      L.m[j[u]][i[u]] = m;
-      L.v[j[u]][i[u]] = v;
-      L.p[j[u]][i[u]] = p[u] + neg_step * (m / (sqrtf(v) / bc2s + epsf));
+      const AdamElem r = adam_element(ac, g0[u], p[u], m0[u], v0[u]);
+      if constexpr (!SELF) L.g[j[u]][i[u]] = r.g;  // (SELF: scaled above)
+      L.m[j[u]][i[u]] = r.m;
+      L.v[j[u]][i[u]] = r.v;
+      L.p[j[u]][i[u]] = r.p;
     }
+  }
+  if constexpr (PREP) {
+    if (!owner) return;
+    const AdamPrepNT& q = pl.nt[((int)blockIdx.x - kAdamBlocks - (lf.partial ? 1 : 0)) / kAdamPrepBlocks];
+    const int lane = threadIdx.x & 63;
+    const bool live = on < q.hp.Nc, two = q.hp.w2 != nullptr;
+    float* p1 = const_cast<float*>(q.hp.w1);
+    float* p2 = const_cast<float*>(q.hp.w2);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {  // each element of the rows has this one owner: the clamped lanes store nothing
+      if (live && !skip && lane + 64 * i < q.hp.k1) {
+        const AdamElem r = adam_element(ac, og[i], op[i], om[i], ov[i]);
+        q.g1[oi[i]] = r.g; q.m1[oi[i]] = r.m; q.v1[oi[i]] = r.v; p1[oi[i]] = r.p;
+        op[i] = r.p;
+      }
+      if (two && live && !skip && lane + 64 * i < q.hp.k2) {
+        const AdamElem r = adam_element(ac, og[6 + i], op[6 + i], om[6 + i], ov[6 + i]);
+        q.g2[oi[6 + i]] = r.g; q.m2[oi[6 + i]] = r.m; q.v2[oi[6 + i]] = r.v; p2[oi[6 + i]] = r.p;
+        op[6 + i] = r.p;
+      }
+    }
+    ws_prep_h2_finish<NTH / 64>(q.hp, on, op);  // column `on` of the image, from the values just stored
   }
 }
 
@@ -495,36 +586,84 @@ extern "C" gnn_status gnn_clip_adam_workspace_size(size_t* bytes) {
   return GNN_OK;
 }
 
-extern "C" gnn_status gnn_clip_adam_f32(const gnn_adam_group* grp, float* step, float* norm_out, void* workspace,
-                                        size_t workspace_bytes, gnn_stream_t stream) {
+// gnn_clip_adam_f32 (nts null) and gnn_clip_adam_prep_f32: every refusal comes before the first launch
+static gnn_status clip_adam_launch(const char* fn, const gnn_adam_group* grp, float* step, float* norm_out,
+                                   void* workspace, size_t workspace_bytes, const gnn_gemm_nt_params* nts,
+                                   int32_t num_nts, gnn_stream_t stream) {
   if (!grp || !step || grp->num_tensors < 0 || grp->num_tensors > GNN_ADAM_MAX_TENSORS)
-    return fail(GNN_ERR_INVALID_ARG, __func__, "bad group");
-  if (!workspace || workspace_bytes < kAdamWsBytes) return fail(GNN_ERR_WORKSPACE, __func__, "workspace too small");
+    return fail(GNN_ERR_INVALID_ARG, fn, "bad group");
+  if (!workspace || workspace_bytes < kAdamWsBytes) return fail(GNN_ERR_WORKSPACE, fn, "workspace too small");
   AdamTable tb{};
   tb.n = grp->num_tensors;
   tb.off[0] = 0;
   for (int j = 0; j < tb.n; ++j) {
     const gnn_adam_tensor& t = grp->tensors[j];
     if (t.numel < 0 || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)))
-      return fail(GNN_ERR_INVALID_ARG, __func__, "bad tensor");
+      return fail(GNN_ERR_INVALID_ARG, fn, "bad tensor");
     tb.p[j] = t.param; tb.g[j] = t.grad; tb.m[j] = t.exp_avg; tb.v[j] = t.exp_avg_sq;
     tb.off[j + 1] = tb.off[j] + t.numel;
   }
   hipStream_t st = (hipStream_t)stream;
   float* partial = static_cast<float*>(workspace);
   LossFinish lf{grp->loss_partial, grp->loss_nblk, grp->loss_scale, grp->loss_out};
-  if (lf.partial && (!lf.out || lf.n < 1)) return fail(GNN_ERR_INVALID_ARG, __func__, "loss_partial needs loss_out and loss_nblk >= 1");
+  if (lf.partial && (!lf.out || lf.n < 1)) return fail(GNN_ERR_INVALID_ARG, fn, "loss_partial needs loss_out and loss_nblk >= 1");
+  if (grp->grad_sq_partial && grp->grad_sq_nblk < 1) return fail(GNN_ERR_INVALID_ARG, fn, "grad_sq_partial needs grad_sq_nblk >= 1");
+  const bool self = !grp->grad_sq_partial && tb.off[tb.n] <= kSelfMax;
+  // the riding B-image preps: their weights leave the flat table `flat` (tb stays whole: the Σg²
+  // pass of the two-launch form sums every gradient in the partition it has always used)
+  AdamPrepList pl{};
+  AdamTable flat = tb;
+  if (nts) {
+    if (num_nts < 1 || num_nts > kAdamMaxPrep) return fail(GNN_ERR_INVALID_ARG, fn, "1 <= num_nts <= 4");
+    if (self) return fail(GNN_ERR_INVALID_ARG, fn, "a group of at most 2^15 elements without grad_sq_partial runs the one-launch form, which builds no image");
+    bool owned[GNN_ADAM_MAX_TENSORS] = {};
+    auto member = [&](const float* w, int64_t numel) {  // the group's tensor behind w, not yet owned
+      for (int j = 0; j < tb.n; ++j)
+        if (w && tb.p[j] == w && grp->tensors[j].numel == numel && !owned[j]) return j;
+      return -1;
+    };
+    for (int i = 0; i < num_nts; ++i) {
+      AdamPrepNT& q = pl.nt[i];
+      if (nt_h2_prep_from_params(&nts[i], &q.hp, fn) != GNN_OK)
+        return fail(GNN_ERR_INVALID_ARG, fn, "the NT params must select the half-pair NT (nt_h2_ok shapes) with its B workspace");
+      if (q.hp.k2 == 0) q.hp.w2 = nullptr;
+      if (q.hp.k1 > 384 || q.hp.k2 > 384 || q.hp.ldw1 != q.hp.k1 || (q.hp.w2 && q.hp.ldw2 != q.hp.k2))
+        return fail(GNN_ERR_INVALID_ARG, fn, "the weights' rows must be contiguous (ldw = k <= 384)");
+      const int j1 = member(q.hp.w1, (int64_t)q.hp.Nc * q.hp.k1);
+      if (j1 >= 0) owned[j1] = true;
+      const int j2 = q.hp.w2 ? member(q.hp.w2, (int64_t)q.hp.Nc * q.hp.k2) : -1;
+      if (j2 >= 0) owned[j2] = true;
+      if (j1 < 0 || (q.hp.w2 && j2 < 0))
+        return fail(GNN_ERR_INVALID_ARG, fn, "w1 / w2 must be whole [N, k] tensors of the group, each under one NT");
+      q.g1 = tb.g[j1]; q.m1 = tb.m[j1]; q.v1 = tb.v[j1];
+      if (j2 >= 0) { q.g2 = tb.g[j2]; q.m2 = tb.m[j2]; q.v2 = tb.v[j2]; }
+    }
+    pl.n = num_nts;
+    flat = AdamTable{};
+    for (int j = 0; j < tb.n; ++j) {
+      if (owned[j]) continue;
+      const int k = flat.n++;
+      flat.p[k] = tb.p[j]; flat.g[k] = tb.g[j]; flat.m[k] = tb.m[j]; flat.v[k] = tb.v[j];
+      flat.off[k + 1] = flat.off[k] + grp->tensors[j].numel;
+    }
+  }
+  const int own = pl.n * kAdamPrepBlocks;
   if (grp->grad_sq_partial) {  // ABI 20: the norm partials came with the gradients (the TN's reduce)
-    if (grp->grad_sq_nblk < 1) return fail(GNN_ERR_INVALID_ARG, __func__, "grad_sq_partial needs grad_sq_nblk >= 1");
     const int nb = grp->grad_sq_nblk;
-    clip_adam_kernel<<<kAdamBlocks + (lf.partial ? 1 : 0), kAdamThreads, 0, st>>>(tb, grp->grad_sq_partial, nb, nb, 2 * nb, step,
+    const int grid = kAdamBlocks + (lf.partial ? 1 : 0);
+    if (own)
+      clip_adam_kernel<kAdamThreads, false, true><<<grid + own, kAdamThreads, 0, st>>>(
+          flat, grp->grad_sq_partial, nb, nb, 2 * nb, step, grp->max_norm, grp->lr, grp->beta1, grp->beta2, grp->eps,
+          grp->weight_decay, norm_out, grp->skip_nonfinite, grp->bump_counter, lf, nullptr, pl);
+    else
+      clip_adam_kernel<<<grid, kAdamThreads, 0, st>>>(tb, grp->grad_sq_partial, nb, nb, 2 * nb, step,
                                                            grp->max_norm, grp->lr, grp->beta1, grp->beta2, grp->eps,
                                                            grp->weight_decay, norm_out, grp->skip_nonfinite,
                                                            grp->bump_counter, lf);
     GNN_LAUNCH_CHECK();
     return GNN_OK;
   }
-  if (tb.off[tb.n] <= kSelfMax) {  // one launch: every block sums Σg² itself
+  if (self) {  // one launch: every block sums Σg² itself
     unsigned* done = reinterpret_cast<unsigned*>(partial + 2 * kAdamBlocks + 1);
     clip_adam_kernel<kSelfThreads, true><<<kAdamBlocks + (lf.partial ? 1 : 0), kSelfThreads, 0, st>>>(
         tb, partial, 0, 0, 0, step, grp->max_norm, grp->lr, grp->beta1, grp->beta2, grp->eps, grp->weight_decay,
@@ -534,10 +673,27 @@ extern "C" gnn_status gnn_clip_adam_f32(const gnn_adam_group* grp, float* step, 
   }
   grad_sq_kernel<<<kAdamBlocks, kAdamThreads, 0, st>>>(tb, partial, step, lf);
   GNN_LAUNCH_CHECK();
-  clip_adam_kernel<<<kAdamBlocks, kAdamThreads, 0, st>>>(tb, partial, kAdamBlocks, kAdamBlocks + 1, kAdamBlocks, step,
-                                                         grp->max_norm, grp->lr, grp->beta1, grp->beta2, grp->eps,
-                                                         grp->weight_decay, norm_out, grp->skip_nonfinite,
-                                                         grp->bump_counter, LossFinish{});
+  if (own)
+    clip_adam_kernel<kAdamThreads, false, true><<<kAdamBlocks + own, kAdamThreads, 0, st>>>(
+        flat, partial, kAdamBlocks, kAdamBlocks + 1, kAdamBlocks, step, grp->max_norm, grp->lr, grp->beta1, grp->beta2,
+        grp->eps, grp->weight_decay, norm_out, grp->skip_nonfinite, grp->bump_counter, LossFinish{}, nullptr, pl);
+  else
+    clip_adam_kernel<<<kAdamBlocks, kAdamThreads, 0, st>>>(tb, partial, kAdamBlocks, kAdamBlocks + 1, kAdamBlocks, step,
+                                                           grp->max_norm, grp->lr, grp->beta1, grp->beta2, grp->eps,
+                                                           grp->weight_decay, norm_out, grp->skip_nonfinite,
+                                                           grp->bump_counter, LossFinish{});
   GNN_LAUNCH_CHECK();
   return GNN_OK;
+}
+
+extern "C" gnn_status gnn_clip_adam_f32(const gnn_adam_group* grp, float* step, float* norm_out, void* workspace,
+                                        size_t workspace_bytes, gnn_stream_t stream) {
+  return clip_adam_launch(__func__, grp, step, norm_out, workspace, workspace_bytes, nullptr, 0, stream);
+}
+
+extern "C" gnn_status gnn_clip_adam_prep_f32(const gnn_adam_group* grp, float* step, float* norm_out, void* workspace,
+                                             size_t workspace_bytes, const gnn_gemm_nt_params* nts, int32_t num_nts,
+                                             gnn_stream_t stream) {
+  if (!nts) return fail(GNN_ERR_INVALID_ARG, __func__, "null nts (gnn_clip_adam_f32 builds no image)");
+  return clip_adam_launch(__func__, grp, step, norm_out, workspace, workspace_bytes, nts, num_nts, stream);
 }

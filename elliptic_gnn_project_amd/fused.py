@@ -500,7 +500,11 @@ class _FusedSAGE(torch.autograd.Function):
                     keep = (kb, Wl[l].size(0), train_drop, seeds[l], seed_ctr)
                     nt_kw = dict(nt_kw, keep_mask=kb)
                 n_out = Wl[l].size(0)
-                ws, side, ready = _nt_workspace(h.device, n_out, im.k1, im.k2), None, False
+                # the B workspace: persistent where ClipAdam's launch may build the image for the next forward
+                ride = isinstance(im, HalfPairImage) and adam_prep_on()
+                ws = (im.b_workspace(Wl[l], Wr[l], _nt_ws_bytes(n_out, im.k1, im.k2) // 4) if ride
+                      else _nt_workspace(h.device, n_out, im.k1, im.k2))
+                side, ready = None, False
                 prep_b = None
                 if _K1_PREP and isinstance(im, HalfPairImage):  # the B prep inside K1's launch, when K1 runs
                     prep_b = lambda: gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="params", **nt_kw)  # noqa: E731
@@ -517,7 +521,14 @@ class _FusedSAGE(torch.autograd.Function):
                     cur.wait_stream(side)
                 if prep_b is not None and not hit:
                     ready = True  # the prep rode in K1's launch
-                # not ready (a hit: no K1 to ride in): the NT call launches its own B-image prep
+                if ride:
+                    req = AdamPrep(gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="params", **nt_kw),
+                                   ws, Wl[l], Wr[l], im)
+                    # ... or in the last optimizer launch, for exactly these weights, image and workspace
+                    ready = ready or _adam_prep_ready(h.device, req)
+                    if any(ctx.needs_input_grad):  # a training forward: the next optimizer step may build it
+                        _ADAM_PREP_REQ[h.device] = req
+                # not ready (a hit with no valid tag): the NT call launches its own B-image prep
                 hn = gemm_nt(None, None, n_out, planes=im, workspace=ws, b_stage="ready" if ready else None, **nt_kw)
                 agg = None
             else:
@@ -815,6 +826,7 @@ class deferred_seed_bumps:
     def __init__(self, defer_loss: bool = False):
         self.defer_loss = bool(defer_loss)
         self.held = []
+        self.preps = []  # the AdamPrep requests whose images the captured optimizer launch builds
 
     def __enter__(self):
         _BUMP_DEFER[0] = self
@@ -856,6 +868,80 @@ def take_seed_bump(device: torch.device):
     if not _deferring():
         return None
     return _PENDING_BUMP.pop(device, None)
+
+
+# The layer-0 half-pair NT's B image built in the optimizer's launch (gnn_clip_adam_prep_f32): the
+# image depends only on the weights, and ClipAdam's launch is their last writer.  A forward whose
+# mean half was cached (no K1 to carry the prep) registers a request; ClipAdam.step takes it, lets
+# its row-owner blocks build the image in the NT's persistent workspace and records a tag; the
+# next forward runs the NT "ready" only when the tag still describes its weights, image and
+# workspace — anything else (a first step, another optimizer, edited weights or x) launches the
+# prep as before.  GNNMP_ADAM_PREP=0, read at every call, keeps the prep in the NT call (A/B).
+class AdamPrep:
+    """One NT's request: its "params"-stage GnnGemmNTParams, workspace, weights and image."""
+
+    def __init__(self, params, ws, w1, w2, im):
+        self.params, self.ws, self.w1, self.w2, self.im = params, ws, w1, w2, im
+
+    def key(self):
+        """What the built image depends on, as far as the host can tell (the kernels write the
+        weights without touching ``_version``: ClipAdam.step voids the tag itself)."""
+        def wkey(w):
+            return None if w is None else (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()))
+
+        p, im = self.params, self.im
+        return (wkey(self.w1), wkey(self.w2), id(im), im.x_key, int(im.exp), self.ws.data_ptr(),
+                int(p.N), int(p.k1), int(p.k2), int(im.col2), int(im.ld))
+
+    def versions(self):
+        return (self.w1._version, self.w2._version if self.w2 is not None else 0)
+
+    def prep(self) -> None:
+        """The standalone prep over the weights as they are now (gnn_gemm_nt_prep_b)."""
+        _lib.call("gnn_gemm_nt_prep_b", self.params, _lib.stream_handle(self.ws.device))
+
+
+_ADAM_PREP_REQ = {}  # device -> the AdamPrep this step's forward registered
+_ADAM_PREP_TAG = {}  # device -> (AdamPrep whose image the last ClipAdam.step built, its key then)
+_ADAM_WRITES = [0]   # ClipAdam.step calls so far: launches that wrote weights without moving a _version
+
+
+def adam_prep_on() -> bool:
+    return os.environ.get("GNNMP_ADAM_PREP", "1") != "0"
+
+
+def take_adam_prep(device: torch.device):
+    """The request of this step's forward (or None); whatever tag the device had is void from here:
+    the caller is about to write the weights."""
+    _ADAM_PREP_TAG.pop(device, None)
+    _ADAM_WRITES[0] += 1
+    return _ADAM_PREP_REQ.pop(device, None)
+
+
+def adam_prep_done(device: torch.device, req: AdamPrep) -> None:
+    """ClipAdam's launch built req's image from the weights it left."""
+    _ADAM_PREP_TAG[device] = (req, req.key())
+    if _BUMP_DEFER[0] is not None and torch.cuda.is_current_stream_capturing():
+        _BUMP_DEFER[0].preps.append(req)  # the capturing CapturedStep guards its replays with it
+
+
+def adam_writes() -> int:
+    """A count that moves whenever a ClipAdam.step was called (eagerly or into a capture)."""
+    return _ADAM_WRITES[0]
+
+
+def adam_prep_replayed(preps) -> None:
+    """A captured step is about to replay: its optimizer launch writes weights behind every tag's
+    back, so all tags are void — except that afterwards the images of ``preps`` (the graph's own
+    requests) are the ones its launch built."""
+    _ADAM_PREP_TAG.clear()
+    for r in preps:
+        _ADAM_PREP_TAG[r.ws.device] = (r, r.key())
+
+
+def _adam_prep_ready(device: torch.device, req: AdamPrep) -> bool:
+    tag = _ADAM_PREP_TAG.get(device)
+    return tag is not None and tag[0].ws is req.ws and tag[1] == req.key()
 
 
 def flush_seed_bumps() -> None:

@@ -234,6 +234,26 @@ class HalfPairImage(SplitImage):
             kb = self._keep = torch.empty((self.n, 4), dtype=torch.int32, device=self.img.device)
         return kb
 
+    _B_WS_MAX = 8  # sets of weights whose workspace one image keeps (the oldest leaves first)
+
+    def b_workspace(self, w1: torch.Tensor, w2, nfloats: int) -> torch.Tensor:
+        """The persistent B workspace (B image + column scales) of this image's half-pair NT over
+        the Linear weights w1 / w2, one per (image, weights): what the optimizer's launch builds
+        for the next forward (fused.adam_prep_*, gnn_clip_adam_prep_f32).  Allocated on first use
+        — the eager warm-up, before any capture; a CapturedStep whose graph reads one holds it."""
+        held = getattr(self, "_b_ws", None)
+        if held is None:
+            held = self._b_ws = {}
+        key = (w1.data_ptr(), w2.data_ptr() if w2 is not None else 0)
+        ws = held.get(key)
+        if ws is None or ws.numel() < nfloats:
+            ws = torch.empty(max(int(nfloats), 1), dtype=torch.float32, device=self.img.device)
+            held.pop(key, None)
+            while len(held) >= self._B_WS_MAX:
+                held.pop(next(iter(held)))
+            held[key] = ws
+        return ws
+
 
 H2_TOP = 14  # a half-pair image's largest magnitude is pre-scaled into [2^(H2_TOP-1), 2^H2_TOP)
 

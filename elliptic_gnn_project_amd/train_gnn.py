@@ -406,8 +406,24 @@ class CapturedStep:
                     tail()
                     fused.flush_seed_bumps()
         self._held = list(dctx.held)  # buffers a replay still reads at its end (deferred loss partials)
+        # the graph's NT reads a B image that the optimizer launch of the replay before it built
+        # (fused.AdamPrep): held here with its workspace, and rebuilt before a replay whenever
+        # the weights were written from outside since the last one
+        self._preps = [(r, (r.versions(), fused.adam_writes())) for r in dctx.preps]
+
+    def _refresh_preps(self) -> None:
+        """Weights written from outside between replays — load_state_dict / copy_ (their
+        ``_version`` moved) or an eager ClipAdam step (fused.adam_writes moved); a host-side look,
+        no sync: the captured NT runs "ready", so the image is rebuilt here."""
+        for i, (r, seen) in enumerate(self._preps):
+            now = (r.versions(), fused.adam_writes())
+            if now != seen:
+                r.prep()
+                self._preps[i] = (r, now)
+        fused.adam_prep_replayed([r for r, _ in self._preps])
 
     def __call__(self):
+        self._refresh_preps()
         self.graph.replay()
         if self.mid is not None:
             self.mid()

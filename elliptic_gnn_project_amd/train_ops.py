@@ -10,6 +10,7 @@ Both run on the GPU only; the CPU path keeps the ATen ops.
 """
 from __future__ import annotations
 
+import ctypes
 import functools
 import os
 from typing import Iterable
@@ -397,6 +398,7 @@ class ClipAdam(torch.optim.Optimizer):
         self._ws = None
         self._sq = None  # norm partials written by the gradients' producer (grad_sq_request)
         self.last_folded = False  # the last step took them (one launch instead of two)
+        self.last_prep = False  # the last step's launch also built an NT's B image (fused.AdamPrep)
         self._groups = {}
         self.last_norm = None
 
@@ -440,8 +442,22 @@ class ClipAdam(torch.optim.Optimizer):
                                 and _tiles(rec, ps))
             if self.last_folded:  # one launch: Σg² came with the gradients
                 g.grad_sq_partial, g.grad_sq_nblk = rec[4].data_ptr(), rec[3]
-            _lib.call("gnn_clip_adam_f32", g, group["step_t"].data_ptr(), self.last_norm.data_ptr(),
-                      self._ws.data_ptr(), self._ws.numel() * 4, _lib.stream_handle(dev))
+            # the layer-0 NT's B image for the next forward rides too (fused.AdamPrep), when this
+            # launch writes its weights and has row-owner blocks to give (not the one-launch form)
+            from .fused import adam_prep_done, adam_prep_on, take_adam_prep
+
+            req = take_adam_prep(dev)  # (also voids the device's tag: this launch writes weights)
+            ptrs = key[1]
+            self.last_prep = (req is not None and gi == 0 and adam_prep_on()
+                              and (self.last_folded or sum(p.numel() for p in ps) > _lib.ADAM_SELF_MAX)
+                              and req.w1.data_ptr() in ptrs and req.w1.is_contiguous()
+                              and (req.w2 is None or (req.w2.data_ptr() in ptrs and req.w2.is_contiguous())))
+            tail = (group["step_t"].data_ptr(), self.last_norm.data_ptr(), self._ws.data_ptr(), self._ws.numel() * 4)
+            if self.last_prep:
+                _lib.call("gnn_clip_adam_prep_f32", g, *tail, ctypes.byref(req.params), 1, _lib.stream_handle(dev))
+                adam_prep_done(dev, req)
+            else:
+                _lib.call("gnn_clip_adam_f32", g, *tail, _lib.stream_handle(dev))
             g.bump_counter = g.loss_partial = g.loss_out = g.grad_sq_partial = None
             g.loss_nblk, g.loss_scale, g.grad_sq_nblk = 0, 0.0, 0  # (the partials workspace is held by the capturing CapturedStep)
             if len(self.param_groups) == 1:  # the next backward's producer may fold Σg²

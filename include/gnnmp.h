@@ -808,6 +808,21 @@ typedef struct {
 gnn_status gnn_clip_adam_workspace_size(size_t* bytes);
 gnn_status gnn_clip_adam_f32(const gnn_adam_group* group, float* step, float* norm_out, void* workspace,
                              size_t workspace_bytes, gnn_stream_t stream);
+/* (additive to ABI 32) gnn_clip_adam_f32 that also builds, in the same launch, the B images of
+ * num_nts (1 .. 4) half-pair NTs from the weights it has just updated: nts[i] are the params of
+ * those NT calls as gnn_gemm_nt_prep_b takes them (w1 / w2, the image fields, the B workspace).
+ * Afterwards each workspace holds exactly what gnn_gemm_nt_prep_b(&nts[i]) would write for the
+ * updated weights, so the next NT over them runs with b_ready = 1 and no prep launch.  The
+ * update is bit for bit gnn_clip_adam_f32's (params, moments, clipped grads, *step, norm_out).
+ * A step skipped under skip_nonfinite leaves the weights alone and builds the image of the
+ * unchanged weights.  Refused with GNN_ERR_INVALID_ARG before any launch: an nts[i] that does
+ * not select the half-pair NT (its shapes, a large enough workspace); w1 (or w2 when k2 > 0) that
+ * is not the `param` of a group tensor of N·k elements, or is claimed twice; ldw != k; a group
+ * that runs the one-launch form (no grad_sq_partial and at most 2^15 elements).  Every gradient,
+ * moment and parameter element keeps exactly one writer; no block waits for another. */
+gnn_status gnn_clip_adam_prep_f32(const gnn_adam_group* group, float* step, float* norm_out, void* workspace,
+                                  size_t workspace_bytes, const gnn_gemm_nt_params* nts, int32_t num_nts,
+                                  gnn_stream_t stream);
 
 /* ------------------------------------------------------------------------ */
 /* K11 NeighborLoader neighbour sampling (torch_geometric.loader.NeighborLoader + pyg-lib
