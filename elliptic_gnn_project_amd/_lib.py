@@ -240,6 +240,24 @@ LOGREG_REDUCE_UNROLL = 4  # GNN_LOGREG_REDUCE_UNROLL
 ISOTONIC_CHUNK = 128  # GNN_ISOTONIC_CHUNK
 BASELINE_STATUS_ROW, BASELINE_STATUS_NAN = 1, 2
 
+# K21 (additive to ABI 32)
+EPOCH_MAX_TENSORS = 64  # GNN_EPOCH_MAX_TENSORS
+EPOCH_CHUNK_BYTES = 16384  # GNN_EPOCH_CHUNK_BYTES
+
+
+class GnnEpochTensor(ctypes.Structure):
+    _fields_ = [("src", c_ptr), ("dst", c_ptr), ("bytes", c_i64)]
+
+
+class GnnEpochTable(ctypes.Structure):
+    _fields_ = [("num_tensors", c_i32), ("reserved", c_i32), ("tensors", GnnEpochTensor * EPOCH_MAX_TENSORS)]
+
+
+class GnnEpochState(ctypes.Structure):
+    """gnn_epoch_state: the device state block of gnn_epoch_keep_best (32 bytes)."""
+    _fields_ = [("epoch", c_i32), ("bad", c_i32), ("best_epoch", c_i32), ("stop_epoch", c_i32), ("status", c_i32),
+                ("reserved", c_i32), ("best_val", ctypes.c_double)]
+
 
 class GnnExplainStepParams(ctypes.Structure):
     """gnn_explain_step_params (ABI 31): one mask's fused GNNExplainer step (K16)."""
@@ -518,6 +536,9 @@ SIGNATURES = {
     "gnn_isotonic_fit": (
         ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
     "gnn_isotonic_apply": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    # K21 (additive to ABI 32)
+    "gnn_epoch_keep_best": (
+        ctypes.c_int, [c_ptr, c_ptr, c_ptr, ctypes.POINTER(GnnEpochTable), c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
 _LIB: ctypes.CDLL | None = None

@@ -787,6 +787,11 @@ def fusable(model) -> bool:
 _SEED_CTR = {}
 
 
+def seed_counter_start() -> int:
+    """The dropout counter's start value: a function of torch's seed that does not consume the RNG."""
+    return (torch.initial_seed() * 0x9E3779B97F4A7C15 + 1) % (2 ** 62)
+
+
 def _graph_seed_counter(device: torch.device) -> torch.Tensor:
     """Per-device int64 dropout counter for HIP-graph capture.
 
@@ -797,8 +802,7 @@ def _graph_seed_counter(device: torch.device) -> torch.Tensor:
     """
     c = _SEED_CTR.get(device)
     if c is None:  # a fill kernel (capture-safe); start value from the seed without consuming the RNG
-        c = torch.full((1,), (torch.initial_seed() * 0x9E3779B97F4A7C15 + 1) % (2 ** 62), dtype=torch.int64,
-                       device=device)
+        c = torch.full((1,), seed_counter_start(), dtype=torch.int64, device=device)
         _SEED_CTR[device] = c
     return c
 

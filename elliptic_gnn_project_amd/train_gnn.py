@@ -15,7 +15,9 @@ processed graph exists), ``graph_file`` (PyG-free .npz written by dataset_ellipt
 ``device_metrics`` (default false: validation PR-AUC per epoch and the per-timestep test PR-AUC on the
 device, rank_metrics / libgnnmp K14; full-batch on a CUDA device only — the mini-batch path keeps the
 host metrics), ``device_eval`` (default false: temperature fit, decision threshold and the metrics.json
-record on the device, calibrate / rank_metrics / libgnnmp K17).
+record on the device, calibrate / rank_metrics / libgnnmp K17), ``epoch_block`` (default 0: K >= 1 runs the
+full-batch loop as blocks of K replays of one captured epoch with the best-state / early-stopping bookkeeping
+on the device, epoch_loop / libgnnmp K21).
 The mini-batch path (:212-245, :260-276, :329-348) runs on loader.NeighborLoader (K11 sampling).
 """
 from __future__ import annotations
@@ -640,7 +642,21 @@ def main(cfg: Dict) -> Dict:
     NLL (calibrate.fit_temperature, one launch) instead of the LBFGS fit, and the decision threshold,
     ``metrics.json`` and ``metrics_hub_removed.json`` come from the device probabilities through
     rank_metrics.select_threshold / evaluation_record (libgnnmp K17); files and keys are unchanged.
-    Partitioned runs gather first, as without the key, and T is still broadcast."""
+    Partitioned runs gather first, as without the key, and T is still broadcast.
+
+    New optional key ``epoch_block`` (integer K >= 1; absent or 0: the loop below, untouched): on a CUDA
+    device, full-batch, one rank, with a capture-safe step (ClipAdam, the fused CE, AMP off or its exact
+    fused form) the epoch — train step, evaluation forward, validation AP and the best-state / early-stopping
+    bookkeeping (libgnnmp K21) — is one captured HIP graph, replayed K times between two looks of the host
+    (epoch_loop.EpochLoop).  It implies ``device_metrics``; the dropout masks then come from the device
+    counter of a captured step, so the run is a reproducible stream of its own (the same bytes for every K),
+    not the bytes of the key-absent run.  Where it cannot apply, one ``[LOOP] epoch_block ignored`` line
+    is printed and the loop below runs; ``world_size`` > 1 raises."""
+    epoch_block = int(cfg.get("epoch_block", 0) or 0)
+    if epoch_block < 0:
+        raise ValueError(f"epoch_block={epoch_block}: an integer >= 1 (0 or absent: off)")
+    if epoch_block and int(cfg.get("world_size", os.environ.get("WORLD_SIZE", "1")) or 1) > 1:
+        raise NotImplementedError("epoch_block with world_size > 1: the captured epoch loop is single-device")
     dist, world, rank = _init_distributed(cfg)
     set_seed(cfg.get("seed", 42))  # same seed on every rank: identical initial weights
     is_main = rank == 0
@@ -689,6 +705,19 @@ def main(cfg: Dict) -> Dict:
 
     device_metrics = bool(cfg.get("device_metrics", False)) and device.type == "cuda" and not use_mini_batch
     device_eval = bool(cfg.get("device_eval", False))
+    loop = None
+    if epoch_block:
+        from . import epoch_loop
+
+        why = epoch_loop.ignored_reason(device, use_mini_batch, opt, loss_fn, use_amp, n_train)
+        if why is not None:
+            print(f"[LOOP] epoch_block ignored: {why}")
+        else:
+            device_metrics = True
+            loop = epoch_loop.EpochLoop(model, data, ei, opt, loss_fn, cfg, device, n_train=n_train,
+                                        val_mask=data.val_mask, patience=cfg.get("patience", 20),
+                                        max_epochs=cfg["max_epochs"], use_amp=use_amp, scaler=scaler, logger=logger,
+                                        verbose=is_main)
     if device_metrics:
         from . import rank_metrics
 
@@ -696,7 +725,9 @@ def main(cfg: Dict) -> Dict:
 
     best_val, best_state, bad = -1.0, None, 0
     patience = cfg.get("patience", 20)
-    for epoch in range(1, cfg["max_epochs"] + 1):
+    if loop is not None:  # the whole loop as blocks of replayed epochs; the best state is loaded in place
+        best_val = loop.run(block=epoch_block)["best_val"]
+    for epoch in range(1, (cfg["max_epochs"] if loop is None else 0) + 1):
         if use_mini_batch:
             loss = train_epoch_minibatch(model, train_loader, opt, loss_fn, scaler, use_amp, cfg, device)
             y_val, p_val = eval_val_minibatch(model, val_loader, device)

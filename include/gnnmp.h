@@ -1276,6 +1276,63 @@ gnn_status gnn_isotonic_fit(const float* scores, const int32_t* order, const uin
 gnn_status gnn_isotonic_apply(const double* xs, const double* ys, const int64_t* K, const float* queries,
                               int64_t n, double* out64, float* out32, int32_t* status, gnn_stream_t stream);
 
+/* ------------------------------------------------------------------------ */
+/* K21 epoch loop (additive to ABI 32: new symbols and new structs only): the best-state and
+ *     early-stopping bookkeeping of train_gnn.main's epoch loop (src/train_gnn.py:371-392) on the
+ *     device, so that an epoch needs no host decision (epoch_loop.py)                               */
+/* ------------------------------------------------------------------------ */
+#define GNN_EPOCH_MAX_TENSORS 64         /* (src, dst, bytes) entries of one call's table */
+#define GNN_EPOCH_CHUNK_BYTES 16384      /* bytes of one entry that one block copies */
+
+typedef struct {
+  const void* src;  /* device; 4-byte aligned */
+  void* dst;        /* device; 4-byte aligned; must not overlap any src */
+  int64_t bytes;    /* >= 0, a multiple of 4; 0: the entry is skipped (src, dst may be NULL) */
+} gnn_epoch_tensor;
+
+typedef struct {
+  int32_t num_tensors; /* 0 .. GNN_EPOCH_MAX_TENSORS */
+  int32_t reserved;
+  gnn_epoch_tensor tensors[GNN_EPOCH_MAX_TENSORS];
+} gnn_epoch_table;
+
+/* the device state block (32 bytes); a run starts from {0, 0, 0, 0, 0, 0, -1.0} */
+typedef struct {
+  int32_t epoch;      /* epochs run so far */
+  int32_t bad;        /* epochs since the best one */
+  int32_t best_epoch; /* 1-based; 0: none yet */
+  int32_t stop_epoch; /* the epoch the run ended on; 0: still running */
+  int32_t status;     /* the AP status bits that ended the run (the host raises for them) */
+  int32_t reserved;
+  double best_val;
+} gnn_epoch_state;
+
+/*
+ * gnn_epoch_keep_best: one epoch's bookkeeping.  ap (f64), ap_status (int32) and loss (f32) are device
+ * scalars read when the launch runs, table a HOST struct read at the call (its pointers travel in the
+ * kernel arguments: a captured launch replays them).  With s = *state:
+ *
+ *   if s.stop_epoch != 0 or s.epoch >= max_epochs: return      (frozen: nothing is read or written)
+ *   e = s.epoch + 1;  s.epoch = e;  loss_log[e-1] = loss;  ap_log[e-1] = ap
+ *   if ap_status != 0:  s.status |= ap_status;  s.stop_epoch = e
+ *   else:
+ *     if ap > s.best_val:  s.best_val = ap;  s.bad = 0;  s.best_epoch = e;  every src -> dst, byte for byte
+ *     else:                s.bad += 1                       (a tie or a NaN ap is "not better")
+ *     if s.bad >= patience or e == max_epochs:  s.stop_epoch = e
+ *
+ * Two launches, so that every block acts on the state as it was before the call: the copy first — each
+ * block takes the decision itself from *state, *ap and *ap_status, none of which that launch writes —
+ * then one thread updates the state and the logs.  The copy moves 16 bytes per lane where src and dst are
+ * both 16-byte aligned (the last bytes % 16 as 4-byte words) and 4-byte words otherwise, one block per
+ * GNN_EPOCH_CHUNK_BYTES of an entry; a table without bytes launches no copy.  loss_log[max_epochs] f32,
+ * ap_log[max_epochs] f64.  INVALID_ARG before any launch: a null pointer, num_tensors outside its range,
+ * an entry with negative bytes, bytes % 4 != 0, or with bytes > 0 a null or misaligned src / dst,
+ * patience < 0, max_epochs < 1.
+ */
+gnn_status gnn_epoch_keep_best(const double* ap, const int32_t* ap_status, const float* loss,
+                               const gnn_epoch_table* table, int32_t patience, int32_t max_epochs,
+                               gnn_epoch_state* state, float* loss_log, double* ap_log, gnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
