@@ -1,5 +1,11 @@
-// Shared pieces of the K7 GEMM kernels (exact-f32 MFMA and split-bf16 MFMA forms):
-// the NT argument block, the dropout counter hash and the fused NT epilogue.
+// What the K7 GEMM files (gemm_f32 / x3 / ws / planes / skinny / dispatch .hip) share:
+//   - NTArgs / TNArgs, the argument blocks every NT / TN kernel takes by value, and H2Prep;
+//   - the dropout counter hash, the bf16 / split-bf16 / half-pair conversions, and nt_epilogue,
+//     the fused NT epilogue of the tiled kernels (gemm_f32.hip, gemm_x3.hip);
+//   - the host helpers the launchers and *_ok predicates are written with: aligned, with_rung,
+//     tn_forms, and the image rules image_cols_ok / image_planes_ok;
+//   - the declarations of every launcher and predicate gemm_dispatch.hip chooses among;
+//   - the half-pair NT's B-image prep (device code shared with train_ops.hip's riding form).
 #pragma once
 #include "common.hpp"
 
@@ -19,6 +25,22 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// ---- host helpers of the launchers and predicates
+// ptr is a multiple of `bytes` (null counts as aligned: the callers test for null where it matters).
+// In a namespace of its own, named by the GEMM files with `using gemm::aligned;`: aggregate.hip, which
+// includes this header too, keeps an `aligned` of its own.
+namespace gemm {
+inline bool aligned(const void* ptr, int bytes) { return (reinterpret_cast<uintptr_t>(ptr) % bytes) == 0; }
+}  // namespace gemm
+
+// A launcher's ladder over a template argument: f(std::integral_constant<int, V>) for the first V of
+// the ascending Vs... with v <= V, else for the last one
+template <int V, int... Vs, typename F>
+void with_rung(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+  else if (v <= V) f(std::integral_constant<int, V>{});
+  else with_rung<Vs...>(v, f);
+}
 
 // Dropout keep decision for element `idx` of a call seeded with `seed`: murmur3's fmix32
 // over (idx * golden + seed_lo) ^ seed_hi, top 24 bits compared with (1-p)·2^24.  32-bit
@@ -55,7 +77,7 @@ struct NTArgs {
   const float* a2; int64_t lda2; int32_t k2;
   const float* bt; int64_t ldb;
   const float* w1; const float* w2; int64_t ldw1, ldw2;  // alternative B: W1 [Nc, k1], W2 [Nc, k2]
-  int32_t wvec2;                                          // W rows 8-byte aligned, k1/k2 even
+  int32_t wvec2;                                          // W rows 8-byte aligned, k1/k2 even (set, but read by no kernel: the slot keeps the layout)
   int32_t wvec;                                           // widest W row vector (1, 2, 4) for the nt2 staging
   float* c; int64_t ldc;
   const float* bias;
@@ -92,14 +114,17 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {  // RNE (v_cvt_pk_bf1
   return __builtin_bit_cast(uint16_t, (__bf16)f);
 }
 
-// Epilogue shared by the NT kernels: bias, ReLU, dropout, store, optional projection.
-// acc[tm][t] is the 32x32 MFMA tile (rows wave·32·TM + tm·32 .., cols n0 + t·32 ..).
-template <int TM, bool CBF = false>
-__device__ __forceinline__ void nt_epilogue(const NTArgs& a, floatx16 (&acc)[TM][4], int64_t m0, int n0, int lane,
+// Epilogue of the tiled NT kernels: bias, ReLU, dropout, store, optional projection.
+// acc[t] is the 32x32 MFMA tile (rows m0 + wave·32 .., cols n0 + t·32 ..).  CBF: C is stored as
+// bf16 (RNE) and the projection reads the rounded values.
+template <bool CBF = false>
+__device__ __forceinline__ void nt_epilogue(const NTArgs& a, floatx16 (&acc)[4], int64_t m0, int n0, int lane,
                                             int wave, uint64_t seed) {
+  // (a loop of one trip, left from a form with several row tiles per wave: without it the compiler
+  // schedules the projection's lane masks differently, and every caller's code is kept as measured)
 #pragma unroll
-  for (int tm = 0; tm < TM; ++tm) {
-    const int64_t rbase = m0 + wave * 32 * TM + tm * 32 + 4 * (lane >> 5);
+  for (int once = 0; once < 1; ++once) {
+    const int64_t rbase = m0 + wave * 32 + 4 * (lane >> 5);
     const uint32_t hstep = (uint32_t)a.Nc * kDropGolden;  // premixed hash step per row
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -110,7 +135,7 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& a, floatx16 (&acc)[TM]
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int64_t row = rbase + (r & 3) + 8 * (r >> 2);
-        float v = acc[tm][t][r] + bv;
+        float v = acc[t][r] + bv;
         if (a.relu) v = fmaxf(v, 0.0f);
         if (a.dropout)  // == keep_elem(seed, row * Nc + col, thresh), bit for bit
           v = keep_premixed(h0 + (uint32_t)((r & 3) + 8 * (r >> 2)) * hstep, seed, a.keep_thresh) ? v * a.drop_scale
@@ -123,7 +148,7 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& a, floatx16 (&acc)[TM]
         } else {
           if (a.c && row < a.M && colok) a.c[row * a.ldc + col] = v;
         }
-        acc[tm][t][r] = v;
+        acc[t][r] = v;
       }
     }
     if (a.nproj > 0) {
@@ -146,10 +171,10 @@ __device__ __forceinline__ void nt_epilogue(const NTArgs& a, floatx16 (&acc)[TM]
         float ps[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          float sum = acc[tm][0][r] * pw[q][0];
-          sum = fmaf(acc[tm][1][r], pw[q][1], sum);
-          sum = fmaf(acc[tm][2][r], pw[q][2], sum);
-          ps[q] = fmaf(acc[tm][3][r], pw[q][3], sum);
+          float sum = acc[0][r] * pw[q][0];
+          sum = fmaf(acc[1][r], pw[q][1], sum);
+          sum = fmaf(acc[2][r], pw[q][2], sum);
+          ps[q] = fmaf(acc[3][r], pw[q][3], sum);
         }
         const float s0 = hi16 ? ps[0] : ps[2], s1 = hi16 ? ps[1] : ps[3];
         const float k0 = (hi16 ? ps[2] : ps[0]) + __shfl_xor(s0, 16);
@@ -182,7 +207,7 @@ struct TNArgs {
   const float* a2; int64_t lda2; int32_t k2;
   float* slab; int64_t slab_stride;
   int64_t rows_per_block;
-  int32_t want_db;
+  int32_t want_db;  // (read by nothing: the slot keeps the layout)
   int32_t a_bf16;  // A1/A2 hold bf16
   int32_t h_bf16;  // h holds bf16
   int32_t g_bf16;  // g (input) and gout (output) hold bf16 (the bf16-image TN)
@@ -201,6 +226,29 @@ struct TNArgs {
   // block writes its whole slab (launch_slab_reduce's `empty`)
   int32_t slab_empty;
 };
+// f(PROJ, MASK, GOUT) as std::bool_constant: the G forms of a TN call — G from dz·P (else read from
+// g), the ReLU / dropout mask of h, the G write-out — which every tiled TN kernel takes as template
+// arguments
+template <typename F>
+void tn_forms(const TNArgs& a, F&& f) {
+  auto pick = [](bool v, auto&& g) { if (v) g(std::true_type{}); else g(std::false_type{}); };
+  pick(a.dz != nullptr, [&](auto proj) {
+    pick(a.h != nullptr, [&](auto mask) { pick(a.gout != nullptr, [&](auto gout) { f(proj, mask, gout); }); });
+  });
+}
+
+// The image of [A1 | A2] an image kernel can read (NTArgs and TNArgs name its fields alike): 16-byte
+// aligned, A1 in columns [0, k1), A2 from an 8-column boundary, both inside a row ...
+template <typename Args>
+bool image_cols_ok(const Args& a) {
+  return gemm::aligned(a.ap, 16) && a.k1 >= 1 && a.k1 <= a.ap_col2 && a.ap_col2 % 8 == 0 && a.ap_col2 + a.k2 <= a.ap_ld;
+}
+// ... and its `planes` planes (16-bit elements) hold M rows each, at byte offsets below 2^31
+template <typename Args>
+bool image_planes_ok(const Args& a, int planes) {
+  return a.ap_ps >= a.M * (int64_t)a.ap_ld && planes * a.ap_ps * 2 < ((int64_t)1 << 31);
+}
+
 // the most 16-row chunks a row block of the flag-driven TN holds (tn_h2_ok bounds M below 1.6 M
 // rows: 2 · ceil(ceil(M / 32) / 256) <= 392); at most one per thread of its 512
 constexpr int TN_ACT_CAP = 512;

@@ -14,10 +14,10 @@
 #include "gemm_common.hpp"
 
 using namespace gnnmp;
+using gemm::aligned;
 
 namespace {
 
-bool aligned(const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; }
 bool bad_dtype(int32_t d) { return d != GNN_DTYPE_F32 && d != GNN_DTYPE_BF16; }
 bool bad_math(int32_t m) { return m != GNN_MATH_SPLIT_BF16 && m != GNN_MATH_F32 && m != GNN_MATH_HALF_PAIR; }
 

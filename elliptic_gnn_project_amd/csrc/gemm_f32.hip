@@ -10,8 +10,13 @@
 //      epi = +bias, ReLU, dropout (counter hash, keep prob 1-p, scale 1/(1-p)),
 //      optional projection Z[M,nproj] = C · Pᵀ (P [nproj, Nc]) — the next, narrow layer's
 //      transform-first GEMM computed from registers (the hidden activations' row is whole
-//      in one wave).  Block = 4 waves x (32 rows x 128 cols); K streamed in 32-deep chunks
-//      through double-buffered LDS (A padded to 33 floats/row: conflict-free b32 reads).
+//      in one wave).  gemm_nt2_kernel<AVEC, BVEC, WFORM>: block = 4 waves x (32 rows x 128 cols);
+//      K streamed in 16-deep chunks (NT_KC) through double-buffered LDS, one chunk of loads in
+//      flight, both operands K-contiguous rows read as b128 fragments.  AVEC / BVEC: widest row
+//      vector of A / W (4, 2, 1); WFORM: B read in place from the Linear weights W1 / W2 [Nc, K],
+//      else from a transposed copy Bt [K, Nc].
+//      Measured and dropped (r01 lab, all slower): a [k][n] B image with scalar b32 fragment
+//      reads (A padded to KC + 1 floats per row), 32-deep chunks, two chunks of loads in flight.
 // TN:  dW[Nr, k1+k2] = Σ_m G[m, Nr]ᵀ · [A1 | A2][m, :]   (split over M, slabs, ordered reduce)
 //      G = (G_src or dz·P) ⊙ (h > 0 ? scale : 0)   — ReLU+dropout backward computed on the fly
 //      side sums: db[n] = Σ G, dW2[q][n] = Σ dz[m,q]·h[m,n], dzsum[q] = Σ dz[m,q]
@@ -24,231 +29,36 @@
 #include "gemm_common.hpp"
 
 namespace gnnmp {
+using gemm::aligned;
 namespace {
 
-constexpr int BNP = BN + 2;  // LDS pitch of the B tile: 2P = 4 mod 32 makes the transposed weight stores (8 lanes x float2 per row) conflict-free
+// ------------------------------------------------------------ NT, k-permuted b128 fragments
+// Both LDS images are K-contiguous rows — A as [row][k], B as [n][k] (the PyTorch Linear weight
+// layout, so W is staged in place) — with a pitch of NT_KC + 4 floats.  MFMA k-step j of k-group g
+// pairs k = 8g+j (lanes 0-31) with k = 8g+4+j (lanes 32-63): each lane fetches the operands of
+// four k-steps with ONE ds_read_b128 (pitch ≡ 20 mod 64 dwords keeps the b128 lane groups
+// conflict-free), 5 LDS reads per 16 MFMAs instead of 20.  Every k is still summed exactly once
+// per output, in a fixed order, with zero-filled tails in both operands.
+constexpr int NT_KC = 16;           // K depth of an LDS chunk
+constexpr int NT_BM = 128;          // block rows (4 waves x 32)
+constexpr int NT_P = NT_KC + 4;     // LDS row pitch, floats
+constexpr int NT_AREG = NT_BM * NT_KC / 256, NT_BREG = BN * NT_KC / 256;  // staged floats per thread
 
-// Tiling parameters: KC = K depth per LDS chunk, TM = 32-row tiles per wave (block rows
-// BM = 4 waves x 32·TM), UNR = fully unroll full chunks.
-template <int KC, int TM>
-struct NTShape {
-  static constexpr int BM = 128 * TM;
-  static constexpr int APITCH = KC + 1;  // odd pitch: conflict-free column reads of A
-  static constexpr int A_PER_THREAD = BM * KC / 256;
-  static constexpr int B_PER_THREAD = KC * BN / 256;
-};
-
-template <int KC>
+// chunk c of [A1 | A2]: its operand, k origin in the segment (k0) and in Bt (kb0), and depth
 __device__ __forceinline__ void nt_chunk_range(const NTArgs& a, int c, const float*& A, int64_t& lda, int& k0,
                                                int& kb0, int& klen) {
+  constexpr int KC = NT_KC;
   const int nch1 = (a.k1 + KC - 1) / KC;
   if (c < nch1) { A = a.a1; lda = a.lda1; k0 = c * KC; kb0 = k0; klen = min(KC, a.k1 - k0); }
   else { A = a.a2; lda = a.lda2; k0 = (c - nch1) * KC; kb0 = a.k1 + k0; klen = min(KC, a.k2 - k0); }
 }
 
-// Loads only (every address clamped into range, no data-dependent selects), so the
-// prefetch of chunk c+1 stays in flight across chunk c's MFMAs; masking happens in
-// nt_store, after them.  AVEC divides k1 and k2, so a vector never straddles K's end.
-template <int AVEC, int KC, int TM>
-__device__ __forceinline__ void nt_load(const NTArgs& a, int c, int64_t m0, int n0, bool bvec4,
-                                        float (&ra)[NTShape<KC, TM>::A_PER_THREAD],
-                                        float (&rb)[NTShape<KC, TM>::B_PER_THREAD]) {
-  using S = NTShape<KC, TM>;
-  const float* A; int64_t lda; int k0, kb0, klen;
-  nt_chunk_range<KC>(a, c, A, lda, k0, kb0, klen);
-  constexpr int VPR = KC / AVEC;
-#pragma unroll
-  for (int i = 0; i < S::A_PER_THREAD / AVEC; ++i) {
-    const int v = threadIdx.x + 256 * i;
-    const int r = v / VPR;
-    const int k = (v % VPR) * AVEC;
-    int64_t row = m0 + r;
-    row = row < a.M ? row : a.M - 1;
-    const float* p = A + row * lda + k0 + (k < klen ? k : 0);
-    if constexpr (AVEC == 4) {
-      float4 t = *reinterpret_cast<const float4*>(p);
-      ra[i * 4 + 0] = t.x; ra[i * 4 + 1] = t.y; ra[i * 4 + 2] = t.z; ra[i * 4 + 3] = t.w;
-    } else if constexpr (AVEC == 2) {
-      float2 t = *reinterpret_cast<const float2*>(p);
-      ra[i * 2 + 0] = t.x; ra[i * 2 + 1] = t.y;
-    } else {
-      ra[i] = *p;
-    }
-  }
-  if (a.w1) {
-    // B from PyTorch Linear weights W [Nc, K] read in place (no transposed copy): 8 lanes cover
-    // KC consecutive k of one weight row with float2 loads (4·KC contiguous bytes).
-    const bool seg1 = c < (a.k1 + KC - 1) / KC;
-    const float* W = seg1 ? a.w1 : a.w2;
-    const int64_t ldw = seg1 ? a.ldw1 : a.ldw2;
-#pragma unroll
-    for (int i = 0; i < S::B_PER_THREAD / 2; ++i) {
-      const int v = threadIdx.x + 256 * i;  // float2 slots: 128 rows x KC/2
-      const int n = v / (KC / 2);
-      const int kk = (v % (KC / 2)) * 2;
-      const int nn = n0 + n < a.Nc ? n0 + n : 0;
-      const float* p = W + (int64_t)nn * ldw + k0 + (kk < klen ? kk : 0);
-      if (a.wvec2) {
-        float2 t = *reinterpret_cast<const float2*>(p);
-        rb[2 * i] = t.x; rb[2 * i + 1] = t.y;
-      } else {
-        rb[2 * i] = p[0];
-        rb[2 * i + 1] = p[kk + 1 < klen ? 1 : 0];
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < S::B_PER_THREAD / 4; ++i) {
-    const int v = threadIdx.x + 256 * i;  // float4 slots: KC rows x 32
-    const int kk = v >> 5;
-    const int n = (v & 31) * 4;
-    const float* p = a.bt + (int64_t)(kb0 + (kk < klen ? kk : 0)) * a.ldb;
-    if (bvec4) {  // Nc % 4 == 0: a float4 never straddles Nc
-      const int nn = n0 + n < a.Nc ? n0 + n : 0;
-      float4 t = *reinterpret_cast<const float4*>(p + nn);
-      rb[i * 4 + 0] = t.x; rb[i * 4 + 1] = t.y; rb[i * 4 + 2] = t.z; rb[i * 4 + 3] = t.w;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) rb[i * 4 + q] = p[n0 + n + q < a.Nc ? n0 + n + q : 0];
-    }
-  }
-}
-
-template <int AVEC, int KC, int TM>
-__device__ __forceinline__ void nt_store(const NTArgs& a, int c, int64_t m0, int n0, float* As, float* Bs,
-                                         const float (&ra)[NTShape<KC, TM>::A_PER_THREAD],
-                                         const float (&rb)[NTShape<KC, TM>::B_PER_THREAD]) {
-  using S = NTShape<KC, TM>;
-  const float* A; int64_t lda; int k0, kb0, klen;
-  nt_chunk_range<KC>(a, c, A, lda, k0, kb0, klen);
-  constexpr int VPR = KC / AVEC;
-#pragma unroll
-  for (int i = 0; i < S::A_PER_THREAD / AVEC; ++i) {
-    const int v = threadIdx.x + 256 * i;
-    const int r = v / VPR;
-    const int k = (v % VPR) * AVEC;
-    const bool ok = (m0 + r < a.M) && (k < klen);
-#pragma unroll
-    for (int q = 0; q < AVEC; ++q) As[r * S::APITCH + k + q] = ok ? ra[i * AVEC + q] : 0.0f;
-  }
-  if (a.w1) {
-#pragma unroll
-    for (int i = 0; i < S::B_PER_THREAD / 2; ++i) {
-      const int v = threadIdx.x + 256 * i;
-      const int n = v / (KC / 2);
-      const int kk = (v % (KC / 2)) * 2;
-      const bool nok = n0 + n < a.Nc;
-      Bs[kk * BNP + n] = (nok && kk < klen) ? rb[2 * i] : 0.0f;
-      Bs[(kk + 1) * BNP + n] = (nok && kk + 1 < klen) ? rb[2 * i + 1] : 0.0f;
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < S::B_PER_THREAD / 4; ++i) {
-    const int v = threadIdx.x + 256 * i;
-    const int kk = v >> 5;
-    const int n = (v & 31) * 4;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) Bs[kk * BNP + n + q] = (kk < klen && n0 + n + q < a.Nc) ? rb[i * 4 + q] : 0.0f;
-  }
-}
-
-template <int KC>
-__device__ __forceinline__ int nt_ksteps(const NTArgs& a, int c) {
-  const float* A; int64_t lda; int k0, kb0, klen;
-  nt_chunk_range<KC>(a, c, A, lda, k0, kb0, klen);
-  return (klen + 1) >> 1;
-}
-
-template <int TM>
-__device__ __forceinline__ void nt_kstep(floatx16 (&acc)[TM][4], const float* Aw, const float* Bw, int s, int apitch) {
-  float af[TM];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm) af[tm] = Aw[tm * 32 * apitch + 2 * s];
-  const float* b = Bw + 2 * s * BNP;
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const float bf = b[t * 32];
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm) acc[tm][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[tm], bf, acc[tm][t], 0, 0, 0);
-  }
-}
-
-
-template <int AVEC, int KC, int TM, bool UNR, int EXP = 0>
-__global__ __launch_bounds__(256) void gemm_nt_kernel(NTArgs a) {
-  using S = NTShape<KC, TM>;
-  __shared__ float As[2][S::BM * S::APITCH];
-  __shared__ float Bs[2][KC * BNP];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int64_t m0 = (int64_t)blockIdx.x * S::BM;
-  const int n0 = blockIdx.y * BN;
-  const int nchunks = (a.k1 + KC - 1) / KC + (a.k2 + KC - 1) / KC;
-  const bool bvec4 = ((a.ldb & 3) == 0) && ((a.Nc & 3) == 0) && ((reinterpret_cast<uintptr_t>(a.bt) & 15) == 0);
-
-  const uint64_t seed = a.seed_ptr ? (*a.seed_ptr) * 0x9E3779B97F4A7C15ull + a.seed : a.seed;
-  floatx16 acc[TM][4];
-#pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][t][r] = 0.0f;
-
-  float ra[S::A_PER_THREAD], rb[S::B_PER_THREAD];
-  nt_load<AVEC, KC, TM>(a, 0, m0, n0, bvec4, ra, rb);
-  nt_store<AVEC, KC, TM>(a, 0, m0, n0, As[0], Bs[0], ra, rb);
-  __syncthreads();
-
-  for (int c = 0; c < nchunks; ++c) {
-    const int buf = c & 1;
-    if (EXP != 1 && EXP != 3 && c + 1 < nchunks) nt_load<AVEC, KC, TM>(a, c + 1, m0, n0, bvec4, ra, rb);
-    const float* Aw = As[buf] + (wave * 32 * TM + (lane & 31)) * S::APITCH + (lane >> 5);
-    const float* Bw = Bs[buf] + (lane >> 5) * BNP + (lane & 31);
-    const int ks = nt_ksteps<KC>(a, c);
-    if (EXP == 2) {
-    } else if (UNR && ks == KC / 2) {
-#pragma unroll
-      for (int s = 0; s < KC / 2; ++s) nt_kstep<TM>(acc, Aw, Bw, s, S::APITCH);
-    } else {
-      for (int s = 0; s < ks; ++s) nt_kstep<TM>(acc, Aw, Bw, s, S::APITCH);
-    }
-    if (EXP != 3 && c + 1 < nchunks) nt_store<AVEC, KC, TM>(a, c + 1, m0, n0, As[buf ^ 1], Bs[buf ^ 1], ra, rb);
-    __syncthreads();
-  }
-
-  nt_epilogue<TM>(a, acc, m0, n0, lane, wave, seed);
-}
-
-template <int AVEC, int KC, int TM, bool UNR, int EXP = 0>
-void launch_nt(const NTArgs& a, hipStream_t st) {
-  dim3 grid((unsigned)ceil_div(a.M, NTShape<KC, TM>::BM), (unsigned)ceil_div(a.Nc, BN));
-  gemm_nt_kernel<AVEC, KC, TM, UNR, EXP><<<grid, 256, 0, st>>>(a);
-}
-
-// ------------------------------------------------------------ NT, k-permuted b128 fragments
-// Both LDS images are K-contiguous rows — A as [row][k], B as [n][k] (the PyTorch Linear weight
-// layout, so W is staged in place) — with a pitch of KC+4 floats.  MFMA k-step j of k-group g
-// pairs k = 8g+j (lanes 0-31) with k = 8g+4+j (lanes 32-63): each lane fetches the operands of
-// four k-steps with ONE ds_read_b128 (pitch ≡ 20 or 36 mod 64 dwords keeps the b128 lane groups
-// conflict-free), 5 LDS reads per 16 MFMAs instead of 20.  Every k is still summed exactly once
-// per output, in a fixed order, with zero-filled tails in both operands.
-template <int KC>
-struct NT2Shape {
-  static constexpr int BM = 128;
-  static constexpr int P = KC + 4;
-  static constexpr int A_PER_THREAD = BM * KC / 256;
-  static constexpr int B_PER_THREAD = BN * KC / 256;
-};
-
 // Stage rows [r0, r0+128) x [k0, k0+KC) of a K-contiguous row-major operand into registers.
 // Row and k are clamped (loads never depend on data: the prefetch stays in flight).
-template <int VEC, int KC>
+template <int VEC>
 __device__ __forceinline__ void nt2_load_rows(const float* X, int64_t ldx, int64_t r0, int64_t rows, int k0,
                                               int klen, float* reg) {
-  constexpr int VPR = KC / VEC;
+  constexpr int KC = NT_KC, VPR = KC / VEC;
 #pragma unroll
   for (int i = 0; i < 128 * KC / 256 / VEC; ++i) {
     const int v = threadIdx.x + 256 * i;
@@ -269,11 +79,10 @@ __device__ __forceinline__ void nt2_load_rows(const float* X, int64_t ldx, int64
   }
 }
 
-template <int VEC, int KC>
+template <int VEC>
 __device__ __forceinline__ void nt2_store_rows(float* L, int64_t r0, int64_t rows, int klen, bool full,
                                                const float* reg) {
-  constexpr int VPR = KC / VEC;
-  constexpr int P = NT2Shape<KC>::P;
+  constexpr int KC = NT_KC, VPR = KC / VEC, P = NT_P;
 #pragma unroll
   for (int i = 0; i < 128 * KC / 256 / VEC; ++i) {
     const int v = threadIdx.x + 256 * i;
@@ -294,8 +103,8 @@ __device__ __forceinline__ void nt2_store_rows(float* L, int64_t r0, int64_t row
 
 // B from the transposed copy Bt [K, Nc] (N-contiguous): lanes run along k so the transposed
 // scalar LDS stores spread over the banks; k and n are clamped.
-template <int KC>
 __device__ __forceinline__ void nt2_load_bt(const NTArgs& a, int kb0, int klen, int n0, bool bvec4, float* reg) {
+  constexpr int KC = NT_KC;
 #pragma unroll
   for (int i = 0; i < BN * KC / 256 / 4; ++i) {
     const int v = threadIdx.x + 256 * i;
@@ -313,9 +122,8 @@ __device__ __forceinline__ void nt2_load_bt(const NTArgs& a, int kb0, int klen, 
   }
 }
 
-template <int KC>
 __device__ __forceinline__ void nt2_store_bt(const NTArgs& a, float* L, int klen, int n0, const float* reg) {
-  constexpr int P = NT2Shape<KC>::P;
+  constexpr int KC = NT_KC, P = NT_P;
 #pragma unroll
   for (int i = 0; i < BN * KC / 256 / 4; ++i) {
     const int v = threadIdx.x + 256 * i;
@@ -326,41 +134,41 @@ __device__ __forceinline__ void nt2_store_bt(const NTArgs& a, float* L, int klen
   }
 }
 
-template <int AVEC, int BVEC, int KC, bool WFORM>
+// one chunk of both operands in registers, between its loads and its LDS stores
+template <int AVEC, int BVEC, bool WFORM>
 struct NT2Stage {
-  using S = NT2Shape<KC>;
-  float ra[S::A_PER_THREAD];
-  float rb[S::B_PER_THREAD];
+  float ra[NT_AREG];
+  float rb[NT_BREG];
   __device__ __forceinline__ void load(const NTArgs& a, int c, int64_t m0, int n0, bool bvec4) {
+    constexpr int KC = NT_KC;
     const float* A; int64_t lda; int k0, kb0, klen;
-    nt_chunk_range<KC>(a, c, A, lda, k0, kb0, klen);
-    nt2_load_rows<AVEC, KC>(A, lda, m0, a.M, k0, klen, ra);
+    nt_chunk_range(a, c, A, lda, k0, kb0, klen);
+    nt2_load_rows<AVEC>(A, lda, m0, a.M, k0, klen, ra);
     if constexpr (WFORM) {
       const bool seg1 = c < (a.k1 + KC - 1) / KC;
-      nt2_load_rows<BVEC, KC>(seg1 ? a.w1 : a.w2, seg1 ? a.ldw1 : a.ldw2, n0, a.Nc, k0, klen, rb);
+      nt2_load_rows<BVEC>(seg1 ? a.w1 : a.w2, seg1 ? a.ldw1 : a.ldw2, n0, a.Nc, k0, klen, rb);
     } else {
-      nt2_load_bt<KC>(a, kb0, klen, n0, bvec4, rb);
+      nt2_load_bt(a, kb0, klen, n0, bvec4, rb);
     }
   }
   __device__ __forceinline__ void store(const NTArgs& a, int c, int64_t m0, int n0, float* As, float* Bs) {
     const float* A; int64_t lda; int k0, kb0, klen;
-    nt_chunk_range<KC>(a, c, A, lda, k0, kb0, klen);
-    const bool kfull = klen == KC;
-    nt2_store_rows<AVEC, KC>(As, m0, a.M, klen, kfull && m0 + S::BM <= a.M, ra);
-    if constexpr (WFORM) nt2_store_rows<BVEC, KC>(Bs, n0, a.Nc, klen, kfull && n0 + BN <= a.Nc, rb);
-    else nt2_store_bt<KC>(a, Bs, klen, n0, rb);
+    nt_chunk_range(a, c, A, lda, k0, kb0, klen);
+    const bool kfull = klen == NT_KC;
+    nt2_store_rows<AVEC>(As, m0, a.M, klen, kfull && m0 + NT_BM <= a.M, ra);
+    if constexpr (WFORM) nt2_store_rows<BVEC>(Bs, n0, a.Nc, klen, kfull && n0 + BN <= a.Nc, rb);
+    else nt2_store_bt(a, Bs, klen, n0, rb);
   }
 };
 
-template <int AVEC, int BVEC, int KC, bool WFORM, int EXP = 0, int DEPTH = 1>
+template <int AVEC, int BVEC, bool WFORM>
 __global__ __launch_bounds__(256) void gemm_nt2_kernel(NTArgs a) {
-  using S = NT2Shape<KC>;
-  constexpr int P = S::P;
-  __shared__ __attribute__((aligned(16))) float As[2][S::BM * P];
+  constexpr int KC = NT_KC, P = NT_P;
+  __shared__ __attribute__((aligned(16))) float As[2][NT_BM * P];
   __shared__ __attribute__((aligned(16))) float Bs[2][BN * P];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int64_t m0 = (int64_t)blockIdx.x * S::BM;
+  const int64_t m0 = (int64_t)blockIdx.x * NT_BM;
   const int n0 = blockIdx.y * BN;
   const int nch1 = (a.k1 + KC - 1) / KC;
   const int nchunks = nch1 + (a.k2 + KC - 1) / KC;
@@ -368,11 +176,11 @@ __global__ __launch_bounds__(256) void gemm_nt2_kernel(NTArgs a) {
                      ((reinterpret_cast<uintptr_t>(a.bt) & 15) == 0);
   const uint64_t seed = a.seed_ptr ? (*a.seed_ptr) * 0x9E3779B97F4A7C15ull + a.seed : a.seed;
 
-  floatx16 acc[1][4];
+  floatx16 acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][t][r] = 0.0f;
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
 
   const int foff = (lane & 31) * P + 4 * (lane >> 5);
   auto compute = [&](const float* Ab, const float* Bb, int c) {
@@ -388,77 +196,30 @@ __global__ __launch_bounds__(256) void gemm_nt2_kernel(NTArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) bv[t] = *reinterpret_cast<const float4*>(Bf + t * 32 * P + 8 * g);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[t].x, acc[0][t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, bv[t].x, acc[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[t].y, acc[0][t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, bv[t].y, acc[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[t].z, acc[0][t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, bv[t].z, acc[t], 0, 0, 0);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[t].w, acc[0][t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, bv[t].w, acc[t], 0, 0, 0);
       }
     }
   };
 
-  if constexpr (DEPTH == 1) {
-    NT2Stage<AVEC, BVEC, KC, WFORM> st;
-    st.load(a, 0, m0, n0, bvec4);
-    st.store(a, 0, m0, n0, As[0], Bs[0]);
+  // one register stage: chunk c + 1's loads are in flight across chunk c's MFMAs
+  NT2Stage<AVEC, BVEC, WFORM> st;
+  st.load(a, 0, m0, n0, bvec4);
+  st.store(a, 0, m0, n0, As[0], Bs[0]);
+  __syncthreads();
+  for (int c = 0; c < nchunks; ++c) {
+    const int buf = c & 1;
+    if (c + 1 < nchunks) st.load(a, c + 1, m0, n0, bvec4);
+    compute(As[buf], Bs[buf], c);
+    if (c + 1 < nchunks) st.store(a, c + 1, m0, n0, As[buf ^ 1], Bs[buf ^ 1]);
     __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-      const int buf = EXP >= 4 ? 0 : (c & 1);
-      if ((EXP == 0 || EXP == 6) && c + 1 < nchunks) st.load(a, c + 1, m0, n0, bvec4);
-      compute(As[buf], Bs[buf], c);
-      if ((EXP == 0 || EXP == 7) && c + 1 < nchunks) st.store(a, c + 1, m0, n0, As[buf ^ 1], Bs[buf ^ 1]);
-      if (EXP == 6 && c + 1 < nchunks) {  // keep the loads alive without the LDS stores
-        float sink = 0.f;
-#pragma unroll
-        for (int i = 0; i < NT2Shape<KC>::A_PER_THREAD; ++i) sink += st.ra[i];
-#pragma unroll
-        for (int i = 0; i < NT2Shape<KC>::B_PER_THREAD; ++i) sink += st.rb[i];
-        if (sink == 12345.678f) As[buf][threadIdx.x] = sink;
-      }
-      if (EXP != 4) __syncthreads();
-    }
-  } else {
-    // Two register stages: while chunk c's MFMAs run, chunks c+1 and c+2 are in flight (one
-    // chunk of MFMAs, ≈0.85 µs, is shorter than a loaded HBM round trip).
-    NT2Stage<AVEC, BVEC, KC, WFORM> s0, s1;
-    s0.load(a, 0, m0, n0, bvec4);
-    s0.store(a, 0, m0, n0, As[0], Bs[0]);
-    __syncthreads();
-    if (1 < nchunks) s1.load(a, 1, m0, n0, bvec4);
-    if (2 < nchunks) s0.load(a, 2, m0, n0, bvec4);
-    for (int c = 0; c < nchunks; c += 2) {
-      compute(As[0], Bs[0], c);
-      if (c + 1 < nchunks) {
-        s1.store(a, c + 1, m0, n0, As[1], Bs[1]);
-        if (c + 3 < nchunks) s1.load(a, c + 3, m0, n0, bvec4);
-      }
-      __syncthreads();
-      if (c + 1 >= nchunks) break;
-      compute(As[1], Bs[1], c + 1);
-      if (c + 2 < nchunks) {
-        s0.store(a, c + 2, m0, n0, As[0], Bs[0]);
-        if (c + 4 < nchunks) s0.load(a, c + 4, m0, n0, bvec4);
-      }
-      __syncthreads();
-    }
   }
-  nt_epilogue<1>(a, acc, m0, n0, lane, wave, seed);
-}
-
-template <int AVEC, int BVEC, int KC, bool WFORM, int EXP, int DEPTH>
-void launch_nt2(const NTArgs& a, hipStream_t st) {
-  dim3 grid((unsigned)ceil_div(a.M, NT2Shape<KC>::BM), (unsigned)ceil_div(a.Nc, BN));
-  gemm_nt2_kernel<AVEC, BVEC, KC, WFORM, EXP, DEPTH><<<grid, 256, 0, st>>>(a);
-}
-
-template <int AVEC, int KC, int EXP = 0, int DEPTH = 1>
-void launch_nt2_b(const NTArgs& a, hipStream_t st) {
-  if (!a.w1) launch_nt2<AVEC, 1, KC, false, EXP, DEPTH>(a, st);
-  else if (a.wvec == 4) launch_nt2<AVEC, 4, KC, true, EXP, DEPTH>(a, st);
-  else if (a.wvec == 2) launch_nt2<AVEC, 2, KC, true, EXP, DEPTH>(a, st);
-  else launch_nt2<AVEC, 1, KC, true, EXP, DEPTH>(a, st);
+  nt_epilogue(a, acc, m0, n0, lane, wave, seed);
 }
 
 // ------------------------------------------------------------------------------------ TN
@@ -778,26 +539,26 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 
 }  // namespace
 
-// The exact-f32 NT: 16-deep chunks, one chunk of loads in flight (r01 lab, the fastest of the
-// [k][n]-image, 32-deep-chunk and two-chunks-in-flight forms).
+// The exact-f32 NT (avec: widest A row vector; a.wvec: widest W row vector; no w1: the Bt form).
 void launch_nt_f32(const NTArgs& a, int avec, hipStream_t st) {
-  if (avec == 4) launch_nt2_b<4, 16>(a, st);
-  else if (avec == 2) launch_nt2_b<2, 16>(a, st);
-  else launch_nt2_b<1, 16>(a, st);
+  const dim3 grid((unsigned)ceil_div(a.M, NT_BM), (unsigned)ceil_div(a.Nc, BN));
+  const int bvec = !a.w1 ? 0 : a.wvec == 4 ? 4 : a.wvec == 2 ? 2 : 1;
+  with_rung<1, 2, 4>(avec == 4 ? 4 : avec == 2 ? 2 : 1, [&](auto av) {
+    with_rung<0, 1, 2, 4>(bvec, [&](auto bv) {
+      gemm_nt2_kernel<av(), (bv() ? bv() : 1), (bv() != 0)><<<grid, 256, 0, st>>>(a);
+    });
+  });
 }
 
 void launch_tn_f32(const TNArgs& a, int nblk, hipStream_t st) {
-  auto al8 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7) == 0; };
-  const bool v2 = (a.k1 % 2 == 0) && (a.lda1 % 2 == 0) && al8(a.a1) &&
-                  (a.k2 == 0 || ((a.k2 % 2 == 0) && (a.lda2 % 2 == 0) && al8(a.a2)));
-  const bool proj = a.dz != nullptr, mask = a.h != nullptr;
-#define GNN_TN(P, MK, V, R) gemm_tn_kernel<P, MK, V, R><<<nblk, TN_THREADS, 0, st>>>(a)
-  // the dz·P + mask prologue holds twice the staging registers: 16-row chunks keep it spill-free
-  if (proj && mask) { if (v2) GNN_TN(true, true, 2, 16); else GNN_TN(true, true, 1, 16); }
-  else if (proj) { if (v2) GNN_TN(true, false, 2, 32); else GNN_TN(true, false, 1, 32); }
-  else if (mask) { if (v2) GNN_TN(false, true, 2, 32); else GNN_TN(false, true, 1, 32); }
-  else { if (v2) GNN_TN(false, false, 2, 32); else GNN_TN(false, false, 1, 32); }
-#undef GNN_TN
+  const bool v2 = (a.k1 % 2 == 0) && (a.lda1 % 2 == 0) && aligned(a.a1, 8) &&
+                  (a.k2 == 0 || ((a.k2 % 2 == 0) && (a.lda2 % 2 == 0) && aligned(a.a2, 8)));
+  tn_forms(a, [&](auto proj, auto mask, auto) {
+    // the dz·P + mask prologue holds twice the staging registers: 16-row chunks keep it spill-free
+    constexpr int MC = (proj() && mask()) ? 16 : 32;
+    if (v2) gemm_tn_kernel<proj(), mask(), 2, MC><<<nblk, TN_THREADS, 0, st>>>(a);
+    else gemm_tn_kernel<proj(), mask(), 1, MC><<<nblk, TN_THREADS, 0, st>>>(a);
+  });
 }
 
 void launch_slab_reduce(const float* slab, int64_t stride, int nred, float* out, int64_t n_out,

@@ -28,6 +28,7 @@ typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
 typedef float f32x2v_t __attribute__((ext_vector_type(2)));
 
 namespace gnnmp {
+using gemm::aligned;
 namespace {
 
 // ------------------------------------------------------------------ split image of an f32 matrix
@@ -1422,83 +1423,38 @@ __global__ __launch_bounds__(256) void gemm_tn_img16_kernel(TNArgs a) {
   }
 }
 
-template <bool PROJ, bool MASK, int KT>
-void launch_tn_img16_k(const TNArgs& a, int nblk, hipStream_t st) {
-  if (a.g_bf16) {
-    if (a.gout) gemm_tn_img16_kernel<PROJ, MASK, KT, true, 4, true><<<nblk, 256, 0, st>>>(a);
-    else gemm_tn_img16_kernel<PROJ, MASK, KT, false, 4, true><<<nblk, 256, 0, st>>>(a);
-    return;
-  }
-  if (a.gout) gemm_tn_img16_kernel<PROJ, MASK, KT, true, 4><<<nblk, 256, 0, st>>>(a);
-  else gemm_tn_img16_kernel<PROJ, MASK, KT, false, 4><<<nblk, 256, 0, st>>>(a);
-}
-
-template <int KT>
-void launch_tn_img16_kt(const TNArgs& a, int nblk, hipStream_t st) {
-  const bool proj = a.dz != nullptr, mask = a.h != nullptr;
-  if (proj && mask) launch_tn_img16_k<true, true, KT>(a, nblk, st);
-  else if (proj) launch_tn_img16_k<true, false, KT>(a, nblk, st);
-  else if (mask) launch_tn_img16_k<false, true, KT>(a, nblk, st);
-  else launch_tn_img16_k<false, false, KT>(a, nblk, st);
-}
-
-template <bool PROJ, bool MASK, int KT>
-void launch_tn_planes_k(const TNArgs& a, int nblk, hipStream_t st) {
-  if (a.Nr <= 64) {  // K split 4 ways over 8 waves (GCN / GAT layer 1, N = 64): lab GCN shape 57.2 ->
-    // 53.8 us vs the 4-wave split-K (profiles/r19_lab_gemm.txt; dW bit-identical)
-    if (a.gout) gemm_tn_planes_kernel<PROJ, MASK, KT, true, 0, 4, 8><<<nblk, 512, 0, st>>>(a);
-    else gemm_tn_planes_kernel<PROJ, MASK, KT, false, 0, 4, 8><<<nblk, 512, 0, st>>>(a);
-    return;
-  }
-  if constexpr (KT <= 8) {  // narrower images at N > 64 (the SAGE-ResBN layer-0 conv over x): K split 2 ways
-    if (a.gout) gemm_tn_planes_kernel<PROJ, MASK, KT, true, 0, 2, 8><<<nblk, 512, 0, st>>>(a);
-    else gemm_tn_planes_kernel<PROJ, MASK, KT, false, 0, 2, 8><<<nblk, 512, 0, st>>>(a);
-    return;
-  }
-  if (a.gout) gemm_tn_planes_kernel<PROJ, MASK, KT, true><<<nblk, 256, 0, st>>>(a);
-  else gemm_tn_planes_kernel<PROJ, MASK, KT, false><<<nblk, 256, 0, st>>>(a);
-}
-
-template <int KT>
-void launch_tn_planes_kt(const TNArgs& a, int nblk, hipStream_t st) {
-  const bool proj = a.dz != nullptr, mask = a.h != nullptr;
-  if (proj && mask) launch_tn_planes_k<true, true, KT>(a, nblk, st);
-  else if (proj) launch_tn_planes_k<true, false, KT>(a, nblk, st);
-  else if (mask) launch_tn_planes_k<false, true, KT>(a, nblk, st);
-  else launch_tn_planes_k<false, false, KT>(a, nblk, st);
-}
-
 }  // namespace
 
 // the bf16 image form: one-plane bf16 image (ld 256 or 336), h bf16 when given
 bool tn_img16_ok(const TNArgs& a) {
   if (!a.ap || a.ap_h2 || !a.a_bf16 || (a.h && !a.h_bf16)) return false;
   // the G slot's vector accesses: 4 columns per row (8-byte h, 16-byte f32 / 8-byte bf16 g and gout rows)
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
   const int gb = a.g_bf16 ? 8 : 16;
-  if (a.Nr % 4 || (a.h && (a.ldh % 4 || !al(a.h, 8))) || (a.g && !a.dz && (a.ldg % 4 || !al(a.g, gb))) ||
-      (a.gout && (a.ldgout % 4 || !al(a.gout, gb))))
+  if (a.Nr % 4 || (a.h && (a.ldh % 4 || !aligned(a.h, 8))) || (a.g && !a.dz && (a.ldg % 4 || !aligned(a.g, gb))) ||
+      (a.gout && (a.ldgout % 4 || !aligned(a.gout, gb))))
     return false;
-  if ((a.ap_ld != 256 && a.ap_ld != 336) || (reinterpret_cast<uintptr_t>(a.ap) & 15)) return false;
-  if (a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 || a.ap_col2 + a.k2 > a.ap_ld) return false;
-  if (a.ap_ps < a.M * (int64_t)a.ap_ld || a.ap_ps * 2 >= ((int64_t)1 << 31) || a.M < PT_ROWS) return false;
+  if ((a.ap_ld != 256 && a.ap_ld != 336) || !image_cols_ok(a) || !image_planes_ok(a, 1) || a.M < PT_ROWS) return false;
   const int64_t ldmax = std::max({a.h ? a.ldh : 0, a.g ? a.ldg : 0, a.dz ? a.lddz : 0});
   return (a.M + 32) * ldmax < ((int64_t)1 << 31);
 }
 
 void launch_tn_img16(const TNArgs& a, int nblk, hipStream_t st) {
-  if (a.ap_ld == 256) launch_tn_img16_kt<8>(a, nblk, st);
-  else launch_tn_img16_kt<11>(a, nblk, st);
+  with_rung<8, 11>(a.ap_ld == 256 ? 8 : 11, [&](auto kt) {
+    tn_forms(a, [&](auto proj, auto mask, auto gout) {
+      if (a.g_bf16) gemm_tn_img16_kernel<proj(), mask(), kt(), gout(), 4, true><<<nblk, 256, 0, st>>>(a);
+      else gemm_tn_img16_kernel<proj(), mask(), kt(), gout(), 4><<<nblk, 256, 0, st>>>(a);
+    });
+  });
 }
 
 // the half-pair forms: the dz form with the h mask (the SAGE hidden layer), f32 h, 336-wide image
 // rows; the plain g form (no dz / h / gout: G read as is, 16-byte aligned rows) over 336- or
 // 176-wide images (x's x-only image: GCN / GAT layer 1, SAGE-ResBN layer 0)
 bool tn_h2_ok(const TNArgs& a) {
-  if (!a.ap || !a.ap_h2 || a.a_bf16 || a.h_bf16 || a.g_bf16 || (reinterpret_cast<uintptr_t>(a.ap) & 15)) return false;
+  if (!a.ap || !a.ap_h2 || a.a_bf16 || a.h_bf16 || a.g_bf16) return false;
   const bool gf = !a.dz && a.g && !a.h && !a.gout;
   if (gf) {
-    if ((a.ap_ld != 336 && a.ap_ld != 176) || a.ldg % 4 || (reinterpret_cast<uintptr_t>(a.g) & 15)) return false;
+    if ((a.ap_ld != 336 && a.ap_ld != 176) || a.ldg % 4 || !aligned(a.g, 16)) return false;
   } else if (!a.dz || !a.proj || !a.h || a.nproj < 1 || a.ap_ld != 336) {
     return false;
   }
@@ -1506,8 +1462,7 @@ bool tn_h2_ok(const TNArgs& a) {
   if (a.cptr && (gf || a.gout || !a.cnbr || !a.cu || a.ccols < 1 || a.ccols > 2 || a.ccols > a.nproj ||
                  a.ldu < a.ccols || a.M * a.ldu >= ((int64_t)1 << 31)))
     return false;
-  if (a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 || a.ap_col2 + a.k2 > a.ap_ld) return false;
-  if (a.ap_ps < a.M * (int64_t)a.ap_ld || 2 * a.ap_ps * 2 >= ((int64_t)1 << 31) || a.M < PT_ROWS) return false;
+  if (!image_cols_ok(a) || !image_planes_ok(a, 2) || a.M < PT_ROWS) return false;
   const int64_t ldmax = gf ? a.ldg : std::max({a.ldh, a.lddz});
   return (a.M + 32) * ldmax < ((int64_t)1 << 31);
 }
@@ -1545,19 +1500,26 @@ void launch_tn_h2(const TNArgs& a, int nblk, hipStream_t st, bool ks, bool act_s
 bool tn_planes_ok(const TNArgs& a) {
   if (!a.ap || a.ap_h2 || a.a_bf16 || a.h_bf16 || a.g_bf16) return false;
   if (a.ap_ld % 16 || a.ap_ld > PT_MAXLD || a.ap_ld < 32) return false;
-  if (a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 || a.ap_col2 + a.k2 > a.ap_ld) return false;
-  if (a.ap_ps < a.M * (int64_t)a.ap_ld || (reinterpret_cast<uintptr_t>(a.ap) & 15)) return false;
-  if (3 * a.ap_ps * 2 >= ((int64_t)1 << 31) || a.M < PT_ROWS) return false;
+  if (!image_cols_ok(a) || !image_planes_ok(a, 3) || a.M < PT_ROWS) return false;
   const int64_t ldmax = std::max({a.h ? a.ldh : 0, a.g ? a.ldg : 0, a.dz ? a.lddz : 0});
   return (a.M + 32) * ldmax < ((int64_t)1 << 31);
 }
 
 void launch_tn_planes(const TNArgs& a, int nblk, hipStream_t st) {
-  const int kt = (a.ap_ld + 31) / 32;
-  if (kt <= 4) launch_tn_planes_kt<4>(a, nblk, st);
-  else if (kt <= 6) launch_tn_planes_kt<6>(a, nblk, st);
-  else if (kt <= 8) launch_tn_planes_kt<8>(a, nblk, st);
-  else launch_tn_planes_kt<11>(a, nblk, st);
+  with_rung<4, 6, 8, 11>((a.ap_ld + 31) / 32, [&](auto kt) {
+    tn_forms(a, [&](auto proj, auto mask, auto gout) {
+      constexpr bool P = proj(), MK = mask(), GO = gout();
+      constexpr int KT = kt();
+      if (a.Nr <= 64) {  // K split 4 ways over 8 waves (GCN / GAT layer 1, N = 64): lab GCN shape 57.2 ->
+        // 53.8 us vs the 4-wave split-K (profiles/r19_lab_gemm.txt; dW bit-identical)
+        gemm_tn_planes_kernel<P, MK, KT, GO, 0, 4, 8><<<nblk, 512, 0, st>>>(a);
+      } else if constexpr (KT <= 8) {  // narrower images at N > 64 (the SAGE-ResBN layer-0 conv over x): K split 2 ways
+        gemm_tn_planes_kernel<P, MK, KT, GO, 0, 2, 8><<<nblk, 512, 0, st>>>(a);
+      } else {
+        gemm_tn_planes_kernel<P, MK, KT, GO><<<nblk, 256, 0, st>>>(a);
+      }
+    });
+  });
 }
 
 }  // namespace gnnmp

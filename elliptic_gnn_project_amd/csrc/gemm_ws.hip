@@ -28,6 +28,7 @@ typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 namespace gnnmp {
+using gemm::aligned;
 namespace {
 
 constexpr int WS_ROWS = 32;            // rows per tile (the MFMA M)
@@ -1339,19 +1340,45 @@ __global__ __launch_bounds__(256) void ws_prep_kernel(NTArgs a, uint4* __restric
   else ws_tail_block(a, tail, r0, blockIdx.x - nchunks);
 }
 
+// The epilogue set (EPI) of a call, passed to f as an integral_constant: plain | bias | bias + ReLU,
+// then + dropout, + projection or both (nt_epi_ok: those need bias + ReLU).  KMASK (the half-pair
+// form): dropout from the call's keep bits when it has them.
+template <int E>
+using epi_c = std::integral_constant<int, E>;
+template <bool KMASK = false, typename F>
+void with_nt_epi(const NTArgs& a, F&& f) {
+  constexpr int ACT = WS_BIAS | WS_RELU;
+  const bool drop = a.dropout != 0, proj = a.nproj > 0;
+  if constexpr (KMASK) {
+    if (drop && a.kmask) {
+      if (proj) f(epi_c<ACT | WS_DROP | WS_PROJ | WS_KMASK>{});
+      else f(epi_c<ACT | WS_DROP | WS_KMASK>{});
+      return;
+    }
+  }
+  if (proj && drop) f(epi_c<ACT | WS_DROP | WS_PROJ>{});
+  else if (proj) f(epi_c<ACT | WS_PROJ>{});
+  else if (drop) f(epi_c<ACT | WS_DROP>{});
+  else if (a.relu) f(epi_c<ACT>{});
+  else if (a.bias) f(epi_c<WS_BIAS>{});
+  else f(epi_c<0>{});
+}
+// the epilogues those sets cover: ReLU comes with bias; dropout and the projection with both
+bool nt_epi_ok(const NTArgs& a) {
+  return (a.relu != 0 && a.bias != nullptr) || !(a.dropout != 0 || a.nproj > 0 || a.relu != 0);
+}
+// the buffer-store epilogue of the f32 forms: 16-byte C rows, whole float4 column chunks, 31-bit
+// byte offsets into C and z
+bool nt_store_ok(const NTArgs& a) {
+  if (a.c && (!aligned(a.c, 16) || a.ldc % 4 != 0 || a.M * a.ldc * 4 >= ((int64_t)1 << 31))) return false;
+  return a.Nc % 4 == 0 && !(a.nproj > 0 && a.M * a.ldz * 4 >= ((int64_t)1 << 31));
+}
+
 template <int NKS, int KS>
 void launch_ws_k(const NTArgs& a, const uint4* bimg, const float* tail, hipStream_t st) {
   const int ntiles = (int)ceil_div(a.M, WS_ROWS);
   const int grid = std::min(ntiles, ws_num_cus());
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-#define GNN_WS(E) gemm_nt_ws_kernel<NKS, E, KS><<<grid, 256 * KS, 0, st>>>(a, bimg, ntiles, tail)
-  if (proj && drop) GNN_WS(WS_BIAS | WS_RELU | WS_DROP | WS_PROJ);
-  else if (proj) GNN_WS(WS_BIAS | WS_RELU | WS_PROJ);
-  else if (drop) GNN_WS(WS_BIAS | WS_RELU | WS_DROP);
-  else if (relu) GNN_WS(WS_BIAS | WS_RELU);
-  else if (bias) GNN_WS(WS_BIAS);
-  else GNN_WS(0);
-#undef GNN_WS
+  with_nt_epi(a, [&](auto e) { gemm_nt_ws_kernel<NKS, e(), KS><<<grid, 256 * KS, 0, st>>>(a, bimg, ntiles, tail); });
 }
 
 }  // namespace
@@ -1361,21 +1388,16 @@ void launch_ws_k(const NTArgs& a, const uint4* bimg, const float* tail, hipStrea
 // an epilogue among plain | bias | bias+ReLU | bias+ReLU+dropout, each + projection when ReLU.
 bool nt_ws_ok(const NTArgs& a) {
   if (a.a_bf16 || a.c_bf16 || !a.w1 || a.Nc > BN || a.Nc < 1) return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (a.lda1 != a.k1 || (a.k1 & 1) || !al(a.a1)) return false;
-  // buffer-store epilogue: 16-byte C rows, whole float4 column chunks, 31-bit byte offsets
-  if (a.c && (!al(a.c) || a.ldc % 4 != 0 || a.M * a.ldc * 4 >= ((int64_t)1 << 31))) return false;
-  if (a.Nc % 4 != 0 || (a.nproj > 0 && a.M * a.ldz * 4 >= ((int64_t)1 << 31))) return false;
-  if (a.k2 > 0 && (a.lda2 != a.k2 || (a.k2 & 1) || !al(a.a2))) return false;
+  if (a.lda1 != a.k1 || (a.k1 & 1) || !aligned(a.a1, 16)) return false;
+  if (!nt_store_ok(a)) return false;
+  if (a.k2 > 0 && (a.lda2 != a.k2 || (a.k2 & 1) || !aligned(a.a2, 16))) return false;
   const int nks = (a.k1 + a.k2 + 15) / 16;
   if (nks != 8 && nks != 11 && nks != 16 && nks != 21) return false;
   if (a.M < WS_ROWS || a.M * (int64_t)std::max(a.k1, a.k2) >= ((int64_t)1 << 40)) return false;
   // the block always computes 128 columns: at N <= 64 half its MFMAs are wasted and the tiled
   // x3 kernel wins (r07: GAT/GCN layer 1, K = 166, N = 64: 104 vs 80 us)
   if (a.Nc <= 64) return false;  // (r22: also slower on SAGE-ResBN's K = 128, N = 64 GEMMs: 1.070 vs 1.053 ms/step)
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-  if ((drop || proj || relu) && !(relu && bias)) return false;
-  return true;
+  return nt_epi_ok(a);
 }
 
 size_t nt_ws_tail_offset(int64_t k1, int64_t k2) {  // the B image (<= 24 chunks x 12 KB), then the tail tile
@@ -1410,16 +1432,8 @@ bool nt_planes_ok(const NTArgs& a) {
   // is bound by its A stream there, not by the MFMA chain)
   if (!a.ap || a.ap_h2 || a.a_bf16 || a.c_bf16 || !a.w1 || (a.k2 > 0 && !a.w2) || a.Nc > BN || a.Nc < 1) return false;
   if (!(a.ap_ld == 336 && a.Nc > 64) && a.ap_ld != 176) return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al(a.ap) || a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 || a.ap_col2 + a.k2 > a.ap_ld)
-    return false;
-  if (a.ap_ps < a.M * (int64_t)a.ap_ld || 3 * a.ap_ps * 2 >= ((int64_t)1 << 31)) return false;
-  if (a.c && (!al(a.c) || a.ldc % 4 != 0 || a.M * a.ldc * 4 >= ((int64_t)1 << 31))) return false;
-  if (a.Nc % 4 != 0 || (a.nproj > 0 && a.M * a.ldz * 4 >= ((int64_t)1 << 31))) return false;
-  if (a.M < WS_ROWS) return false;
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-  if ((drop || proj || relu) && !(relu && bias)) return false;
-  return true;
+  if (!image_cols_ok(a) || !image_planes_ok(a, 3) || !nt_store_ok(a)) return false;
+  return a.M >= WS_ROWS && nt_epi_ok(a);
 }
 
 // The half-pair form: f32 C, the w1/w2 B form, a half-pair image row of 336 (21 k-steps: the
@@ -1427,19 +1441,12 @@ bool nt_planes_ok(const NTArgs& a) {
 // N % 4 == 0, M >= 32, the nt_ws_ok epilogues.
 bool nt_h2_ok(const NTArgs& a) {
   if (!a.ap || !a.ap_h2 || a.a_bf16 || a.c_bf16 || !a.w1 || (a.k2 > 0 && !a.w2) || a.Nc > BN || a.Nc < 1) return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if ((a.ap_ld != 336 && a.ap_ld != 176) || !al(a.ap) || a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 || a.ap_col2 + a.k2 > a.ap_ld)
-    return false;
-  if (a.ap_ps < a.M * (int64_t)a.ap_ld || 2 * a.ap_ps * 2 >= ((int64_t)1 << 31)) return false;
-  if (a.c && (!al(a.c) || a.ldc % 4 != 0 || a.M * a.ldc * 4 >= ((int64_t)1 << 31))) return false;
-  if (a.Nc % 4 != 0 || (a.nproj > 0 && a.M * a.ldz * 4 >= ((int64_t)1 << 31))) return false;
+  if ((a.ap_ld != 336 && a.ap_ld != 176) || !image_cols_ok(a) || !image_planes_ok(a, 2) || !nt_store_ok(a)) return false;
   if (a.M < WS_ROWS) return false;
   // the prep kernel's linear sweep indexes the weights with 32-bit element offsets
   if (a.ldw1 < a.k1 || a.Nc * a.ldw1 >= ((int64_t)1 << 30) || (a.w2 && a.k2 > 0 && (a.ldw2 < a.k2 || a.Nc * a.ldw2 >= ((int64_t)1 << 30))))
     return false;
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-  if ((drop || proj || relu) && !(relu && bias)) return false;
-  return true;
+  return nt_epi_ok(a);
 }
 
 H2Prep h2_prep_of(const NTArgs& a, uint4* img) {
@@ -1468,17 +1475,7 @@ void launch_nt_h2_k(const NTArgs& a, uint4* img, hipStream_t st, int phase) {
   // on 213 blocks of 4 (not 256 blocks of 3 or 4: the same longest block, 17 % fewer B loads)
   const int per = (int)ceil_div(ntiles, ws_num_cus());
   const int grid = (int)ceil_div(ntiles, per);
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-#define GNN_NH(E) gemm_nt_h2_kernel<NKS, E><<<grid, 256, 0, st>>>(a, img, colscale, ntiles)
-  if (proj && drop && a.kmask) GNN_NH(WS_BIAS | WS_RELU | WS_DROP | WS_PROJ | WS_KMASK);
-  else if (drop && a.kmask) GNN_NH(WS_BIAS | WS_RELU | WS_DROP | WS_KMASK);
-  else if (proj && drop) GNN_NH(WS_BIAS | WS_RELU | WS_DROP | WS_PROJ);
-  else if (proj) GNN_NH(WS_BIAS | WS_RELU | WS_PROJ);
-  else if (drop) GNN_NH(WS_BIAS | WS_RELU | WS_DROP);
-  else if (relu) GNN_NH(WS_BIAS | WS_RELU);
-  else if (bias) GNN_NH(WS_BIAS);
-  else GNN_NH(0);
-#undef GNN_NH
+  with_nt_epi<true>(a, [&](auto e) { gemm_nt_h2_kernel<NKS, e()><<<grid, 256, 0, st>>>(a, img, colscale, ntiles); });
 }
 
 void launch_nt_h2(const NTArgs& a, uint4* img, hipStream_t st, int phase) {
@@ -1491,33 +1488,21 @@ void launch_nt_h2(const NTArgs& a, uint4* img, hipStream_t st, int phase) {
 bool nt_img16_ok(const NTArgs& a) {
   if (!a.ap || a.ap_h2 || !a.a_bf16 || !a.c_bf16 || !a.c || !a.w1 || (a.k2 > 0 && !a.w2) || a.Nc > BN || a.Nc < 8 || a.Nc % 8)
     return false;
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  if (!al(a.ap) || (a.ap_ld != 256 && a.ap_ld != 336) || a.k1 < 1 || a.k1 > a.ap_col2 || a.ap_col2 % 8 ||
-      a.ap_col2 + a.k2 > a.ap_ld)
-    return false;
-  if (!al(a.c) || a.ldc % 8 != 0 || a.ldc < a.Nc || a.M * a.ldc * 2 >= ((int64_t)1 << 31)) return false;
+  // (one plane, read by rows: this form has never bounded the plane stride)
+  if ((a.ap_ld != 256 && a.ap_ld != 336) || !image_cols_ok(a)) return false;
+  if (!aligned(a.c, 16) || a.ldc % 8 != 0 || a.ldc < a.Nc || a.M * a.ldc * 2 >= ((int64_t)1 << 31)) return false;
   // the projection is stored as one 16-byte z row: all four products, 16-byte aligned rows
-  if (a.nproj > 0 && (a.nproj != MAXPROJ || a.ldz % 4 != 0 || !al(a.z) || a.M * a.ldz * 4 >= ((int64_t)1 << 31)))
+  if (a.nproj > 0 && (a.nproj != MAXPROJ || a.ldz % 4 != 0 || !aligned(a.z, 16) || a.M * a.ldz * 4 >= ((int64_t)1 << 31)))
     return false;
   if (a.M < WS_ROWS || ceil_div(a.M, WS_ROWS) >= INT32_MAX) return false;
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-  if ((drop || proj || relu) && !(relu && bias)) return false;
-  return true;
+  return nt_epi_ok(a);
 }
 
 template <int NKS>
 void launch_nt_img16_k(const NTArgs& a, const uint4* img, hipStream_t st) {
   const int ntiles = (int)ceil_div(a.M, WS_ROWS);
   const int grid = std::min(ntiles, ws_num_cus());
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-#define GNN_I16(E) gemm_nt_img16_kernel<NKS, E, 4><<<grid, 256, 0, st>>>(a, img, ntiles)
-  if (proj && drop) GNN_I16(WS_BIAS | WS_RELU | WS_DROP | WS_PROJ);
-  else if (proj) GNN_I16(WS_BIAS | WS_RELU | WS_PROJ);
-  else if (drop) GNN_I16(WS_BIAS | WS_RELU | WS_DROP);
-  else if (relu) GNN_I16(WS_BIAS | WS_RELU);
-  else if (bias) GNN_I16(WS_BIAS);
-  else GNN_I16(0);
-#undef GNN_I16
+  with_nt_epi(a, [&](auto e) { gemm_nt_img16_kernel<NKS, e(), 4><<<grid, 256, 0, st>>>(a, img, ntiles); });
 }
 
 void launch_nt_img16(const NTArgs& a, uint4* img, hipStream_t st, int phase) {
@@ -1532,15 +1517,7 @@ template <int NKS>
 void launch_nt_ws_planes_k(const NTArgs& a, uint4* img, hipStream_t st) {
   const int ntiles = (int)ceil_div(a.M, WS_ROWS);
   const int grid = std::min(ntiles, ws_num_cus());
-  const bool drop = a.dropout != 0, relu = a.relu != 0, bias = a.bias != nullptr, proj = a.nproj > 0;
-#define GNN_WSP(E) gemm_nt_planes_kernel<NKS, E><<<grid, 256, 0, st>>>(a, img, ntiles)
-  if (proj && drop) GNN_WSP(WS_BIAS | WS_RELU | WS_DROP | WS_PROJ);
-  else if (proj) GNN_WSP(WS_BIAS | WS_RELU | WS_PROJ);
-  else if (drop) GNN_WSP(WS_BIAS | WS_RELU | WS_DROP);
-  else if (relu) GNN_WSP(WS_BIAS | WS_RELU);
-  else if (bias) GNN_WSP(WS_BIAS);
-  else GNN_WSP(0);
-#undef GNN_WSP
+  with_nt_epi(a, [&](auto e) { gemm_nt_planes_kernel<NKS, e()><<<grid, 256, 0, st>>>(a, img, ntiles); });
 }
 
 void launch_nt_ws_planes(const NTArgs& a, uint4* img, hipStream_t st, int phase) {

@@ -24,6 +24,7 @@ typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 namespace gnnmp {
+using gemm::aligned;
 namespace {
 
 __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {  // RNE, a in the low half
@@ -90,13 +91,21 @@ __device__ __forceinline__ const float* elem_ptr(const float* p, int64_t e) {
 }
 
 // ------------------------------------------------------------------------------------- NT
-// Stage rows [r0, r0+ROWS) x [k0, k0+KC) of a K-contiguous f32 operand into registers, in units
+// The NT kernels of this file (gemm_nt_x3_kernel, gemm_nt_h2s_kernel) tile alike: blocks of 128 rows
+// x BN = 128 columns, K in 16-deep chunks (one MFMA k-step), LDS rows of 16 + 8 bf16 / f16.
+// (Measured and dropped, r05-r10: 32-deep chunks, two 32-row tiles per wave — launch_nt_x3.)
+constexpr int XKC = 16;         // K depth of a chunk
+constexpr int XROWS = 128;      // rows of a staged operand (block rows, and BN)
+constexpr int XP = XKC + 8;     // 16-bit elements per LDS row: 12 dwords (conflict-free b128)
+
+// Stage rows [r0, r0+128) x [k0, k0+16) of a K-contiguous f32 operand into registers, in units
 // of U consecutive k per thread, each loaded as U/V vectors of V floats (V | k1, k2, ld).
 // Addresses are clamped (never data-dependent), so the prefetch stays in flight across the
 // MFMAs; masking happens at the split/store.
-template <int V, int U, int KC, int ROWS, bool BF = false>
+template <int V, int U, bool BF = false>
 __device__ __forceinline__ void x3_load_rows(const float* X, int64_t ldx, int64_t r0, int64_t rows, int k0,
                                              int klen, float* reg) {
+  constexpr int KC = XKC, ROWS = XROWS;
   if constexpr (BF) {  // bf16 rows (ld in elements): V bf16 per load, widened to f32 (exact)
     const uint16_t* X16 = reinterpret_cast<const uint16_t*>(X);
     constexpr int UPR = KC / U;
@@ -150,10 +159,11 @@ __device__ __forceinline__ void x3_load_rows(const float* X, int64_t ldx, int64_
   }
 }
 
-// Split and store into three bf16 planes L[p * ROWS * PITCH + r * PITCH + k] (one b32 / b64 /
-// b128 store per plane for U = 2 / 4 / 8); zero outside (rows, klen).
-template <int U, int KC, int ROWS, int PITCH, int NPL = 3>
+// Split and store into NPL (3, or 1: the hi plane alone) bf16 planes L[p * 128 * XP + r * XP + k]
+// (one b32 / b64 store per plane for U = 2 / 4); zero outside (rows, klen).
+template <int U, int NPL>
 __device__ __forceinline__ void x3_store_rows(uint16_t* L, int64_t r0, int64_t rows, int klen, const float* reg) {
+  constexpr int KC = XKC, ROWS = XROWS, PITCH = XP;
   constexpr int UPR = KC / U;
   constexpr int PL = ROWS * PITCH;
 #pragma unroll
@@ -173,18 +183,17 @@ __device__ __forceinline__ void x3_store_rows(uint16_t* L, int64_t r0, int64_t r
     uint16_t* d = L + r * PITCH + k;
 #pragma unroll
     for (int p = 0; p < NPL; ++p) {
-      if constexpr (U == 8) *reinterpret_cast<uint4*>(d + p * PL) = make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]);
-      else if constexpr (U == 4) *reinterpret_cast<uint2*>(d + p * PL) = make_uint2(w[0][p], w[1][p]);
+      if constexpr (U == 4) *reinterpret_cast<uint2*>(d + p * PL) = make_uint2(w[0][p], w[1][p]);
       else *reinterpret_cast<uint32_t*>(d + p * PL) = w[0][p];
     }
   }
 }
 
-// The half-pair form of x3_store_rows: unit i's row scaled by sc[i] (a power of two, exact), two
-// f16 planes hi / lo; zero outside (rows, klen).
-template <int U, int KC, int ROWS, int PITCH>
+// The half-pair form of x3_store_rows (units of U = 4): unit i's row scaled by sc[i] (a power of
+// two, exact), two f16 planes hi / lo; zero outside (rows, klen).
 __device__ __forceinline__ void h2_store_rows(uint16_t* L, int64_t r0, int64_t rows, int klen, const float* reg,
                                               const float* sc) {
+  constexpr int U = 4, KC = XKC, ROWS = XROWS, PITCH = XP;
   constexpr int UPR = KC / U;
   constexpr int PL = ROWS * PITCH;
 #pragma unroll
@@ -203,11 +212,7 @@ __device__ __forceinline__ void h2_store_rows(uint16_t* L, int64_t r0, int64_t r
     }
     uint16_t* d = L + r * PITCH + k;
 #pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      if constexpr (U == 8) *reinterpret_cast<uint4*>(d + p * PL) = make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]);
-      else if constexpr (U == 4) *reinterpret_cast<uint2*>(d + p * PL) = make_uint2(w[0][p], w[1][p]);
-      else *reinterpret_cast<uint32_t*>(d + p * PL) = w[0][p];
-    }
+    for (int p = 0; p < 2; ++p) *reinterpret_cast<uint2*>(d + p * PL) = make_uint2(w[0][p], w[1][p]);
   }
 }
 
@@ -231,33 +236,37 @@ __global__ __launch_bounds__(256) void x3_presplit_b_kernel(NTArgs a, uint4* __r
   uint32_t w[4][3];
 #pragma unroll
   for (int j = 0; j < 4; ++j) split_pair(e[2 * j], e[2 * j + 1], w[j]);
-  // swz (the LDS-DMA kernel's image): the k-half of row n is stored at kh ^ bit 3 of n, so the
-  // lane-linear DMA copy lands conflict-free for the ds_read_b128 fragment reads
+  // swz (always 0: it served an LDS-DMA kernel that is gone, whose image stored the k-half of row
+  // n at kh ^ bit 3 of n; the argument stays because dropping it changes this kernel's code object)
   const int slot = swz ? 2 * n + (kh ^ ((n >> 3) & 1)) : (idx & 255);
 #pragma unroll
   for (int p = 0; p < 3; ++p) img[((int64_t)c * 3 + p) * 256 + slot] = make_uint4(w[0][p], w[1][p], w[2][p], w[3][p]);
 }
 
-template <int KC>
+// chunk c of [A1 | A2] and [W1 | W2]: its operands, k origin in the segment and depth
 __device__ __forceinline__ void x3_chunk(const NTArgs& a, int c, int nch1, const float*& A, int64_t& lda,
                                          const float*& W, int64_t& ldw, int& k0, int& klen) {
+  constexpr int KC = XKC;
   if (c < nch1) { A = a.a1; lda = a.lda1; W = a.w1; ldw = a.ldw1; k0 = c * KC; klen = min(KC, a.k1 - k0); }
   else { A = a.a2; lda = a.lda2; W = a.w2; ldw = a.ldw2; k0 = (c - nch1) * KC; klen = min(KC, a.k2 - k0); }
 }
 
-// Block: 4 waves, wave w owns rows w·32·TM .. (+32·TM) x all 128 columns (the epilogue's
-// projection needs whole rows in one wave).  K in chunks of KC through double-buffered LDS,
-// fed by a ring of D register stages: chunk c's loads are issued D chunks ahead, so D chunks
-// of A (BM x KC f32) are in flight per block while the MFMAs run (the split MFMA work per chunk
-// is short; without depth the loop waits on HBM latency).  One barrier per chunk.
-// NPL = 3: f32 operands split (6 products); NPL = 1 with ABF: bf16 operands as stored, B rounded
-// to bf16 (the image's hi plane), one product (the bf16-storage path); CBF: C stored as bf16.
-constexpr int NT_PIPE = 32, NT_HINTS = 64;  // gemm_nt_x3_kernel schedule flags (the bf16-storage form)
-
-template <int KC, int TM, int AV, int AU, int BV, int D, int NPL = 3, bool ABF = false, bool CBF = false, int SCHED = 0>
+// Block: 4 waves, wave w owns rows w·32 .. (+32) x all 128 columns (the epilogue's projection
+// needs whole rows in one wave).  K in 16-deep chunks through double-buffered LDS, fed by a ring
+// of D = 2 register stages: chunk c's loads are issued D chunks ahead, so D chunks of A (128 x 16
+// f32) are in flight per block while the MFMAs run (the split MFMA work per chunk is short;
+// without depth the loop waits on HBM latency).  One barrier per chunk.
+// AV: widest A row vector (4, 2, 1).  BV: widest W row vector, B split on the fly from the f32
+// weights; BV = 0: B copied from the pre-split image (x3_presplit_b_kernel).
+// ABF = false: f32 operands split into 3 planes (6 products).  ABF: the bf16-storage path — bf16
+// operands as stored, B rounded to bf16 (the image's hi plane), one product.  CBF: C stored as bf16.
+template <int AV, int BV, bool ABF, bool CBF>
 __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* __restrict__ bimg) {
-  constexpr int P = KC + 8;  // bf16 per LDS row: 24 or 40 (12 / 20 dwords)
-  constexpr int BM = 128 * TM;
+  constexpr int KC = XKC, P = XP, BM = XROWS;
+  constexpr int D = 2;                      // register stages (D = 1 / 3 measured slower: launch_nt_x3)
+  constexpr int NPL = ABF ? 1 : 3;          // planes per operand
+  constexpr int AU = AV < 2 ? 2 : AV;       // k per staging unit of A (a packed bf16 pair at least)
+  constexpr bool PIPE = ABF && BV == 0;     // the software-pipelined order with interleave hints (below)
   constexpr int APL = BM * P, BPL = BN * P;
   constexpr int AREG = BM * KC / 256, BREG = BN * KC / 256;
   __shared__ __attribute__((aligned(16))) uint16_t As[2][NPL * APL];
@@ -270,23 +279,19 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
   const int nchunks = nch1 + (a.k2 + KC - 1) / KC;
   const uint64_t seed = a.seed_ptr ? (*a.seed_ptr) * 0x9E3779B97F4A7C15ull + a.seed : a.seed;
 
-  floatx16 acc[TM][4];
+  floatx16 acc[4];
 #pragma unroll
-  for (int tm = 0; tm < TM; ++tm)
+  for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[tm][t][r] = 0.0f;
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
 
-  // BV > 0: B split on the fly from the f32 weights; BV == 0: B copied from the pre-split image
   constexpr int BU = BV < 2 ? 2 : BV;
-  constexpr int RB = BV == 0 ? 12 : BREG;  // image: 3 planes x uint4 per thread (KC = 16)
-  static_assert(BV > 0 || KC == 16, "pre-split B image is cut in 16-deep chunks");
+  constexpr int RB = BV == 0 ? 12 : BREG;  // image: 3 planes x uint4 per thread
   float ra[D][AREG], rb[D][RB];
   auto load = [&](int c, float* rA, float* rB) {
     const float *A, *W; int64_t lda, ldw; int k0, klen;
-    x3_chunk<KC>(a, c, nch1, A, lda, W, ldw, k0, klen);
-    x3_load_rows<AV, AU, KC, BM, ABF>(A, lda, m0, a.M, k0, klen, rA);
+    x3_chunk(a, c, nch1, A, lda, W, ldw, k0, klen);
+    x3_load_rows<AV, AU, ABF>(A, lda, m0, a.M, k0, klen, rA);
     if constexpr (BV == 0) {
 #pragma unroll
       for (int p = 0; p < NPL; ++p) {
@@ -295,13 +300,13 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
         rB[4 * p + 2] = __uint_as_float(t.z); rB[4 * p + 3] = __uint_as_float(t.w);
       }
     } else {
-      x3_load_rows<BV, BU, KC, BN>(W, ldw, n0, a.Nc, k0, klen, rB);
+      x3_load_rows<BV, BU>(W, ldw, n0, a.Nc, k0, klen, rB);
     }
   };
   auto store = [&](int c, int buf, const float* rA, const float* rB) {
     const float *A, *W; int64_t lda, ldw; int k0, klen;
-    x3_chunk<KC>(a, c, nch1, A, lda, W, ldw, k0, klen);
-    x3_store_rows<AU, KC, BM, P, NPL>(As[buf], m0, a.M, klen, rA);
+    x3_chunk(a, c, nch1, A, lda, W, ldw, k0, klen);
+    x3_store_rows<AU, NPL>(As[buf], m0, a.M, klen, rA);
     if constexpr (BV == 0) {
       const int n = threadIdx.x >> 1, kh = threadIdx.x & 1;
 #pragma unroll
@@ -310,32 +315,22 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
             make_uint4(__float_as_uint(rB[4 * p]), __float_as_uint(rB[4 * p + 1]), __float_as_uint(rB[4 * p + 2]),
                        __float_as_uint(rB[4 * p + 3]));
     } else {
-      x3_store_rows<BU, KC, BN, P, NPL>(Bs[buf], n0, a.Nc, klen, rB);
+      x3_store_rows<BU, NPL>(Bs[buf], n0, a.Nc, klen, rB);
     }
   };
   const int fr = (lane & 31) * P + 8 * (lane >> 5);
-  auto compute = [&](int buf, int c) {
-    const int klen = c < nch1 ? min(KC, a.k1 - c * KC) : min(KC, a.k2 - (c - nch1) * KC);
-    const uint16_t* Ab = As[buf] + wave * 32 * TM * P + fr;
+  auto compute = [&](int buf) {  // one k-step: every chunk has klen >= 1, its tail zero-filled
+    const uint16_t* Ab = As[buf] + wave * 32 * P + fr;
     const uint16_t* Bb = Bs[buf] + fr;
+    bf16x8 af[NPL], bf[4][NPL];
 #pragma unroll
-    for (int s = 0; s < KC / 16; ++s) {
-      if (KC == 16 || 16 * s < klen) {  // KC == 16: every chunk has klen >= 1 (no branch)
-        bf16x8 af[TM][NPL], bf[4][NPL];
+    for (int p = 0; p < NPL; ++p) af[p] = lds_frag(Ab + p * APL);
 #pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
-          for (int p = 0; p < NPL; ++p) af[tm][p] = lds_frag(Ab + p * APL + tm * 32 * P + 16 * s);
+      for (int p = 0; p < NPL; ++p) bf[t][p] = lds_frag(Bb + p * BPL + t * 32 * P);
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int p = 0; p < NPL; ++p) bf[t][p] = lds_frag(Bb + p * BPL + t * 32 * P + 16 * s);
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-          for (int tm = 0; tm < TM; ++tm) acc[tm][t] = mfma_planes<NPL>(af[tm], bf[t], acc[tm][t]);
-      }
-    }
+    for (int t = 0; t < 4; ++t) acc[t] = mfma_planes<NPL>(af, bf[t], acc[t]);
   };
 
   // Loads are unconditional (a clamped chunk index: the tail re-reads the last chunk) so the
@@ -343,7 +338,7 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
   // in flight; a branch around a load makes it drain every stage at the next store.
 #pragma unroll
   for (int d = 0; d < D; ++d) load(min(d, nchunks - 1), ra[d], rb[d]);
-  if constexpr ((SCHED & NT_PIPE) != 0) {
+  if constexpr (PIPE) {
     // software-pipelined order: between two barriers, stage chunk c+1 into the other buffer
     // while the MFMAs of chunk c run, so VALU splits / LDS writes interleave with the MFMAs
     store(0, 0, ra[0], rb[0]);
@@ -357,16 +352,14 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
         __syncthreads();
         store(cc + 1, (cc + 1) & 1, ra[d1], rb[d1]);
         load(min(cc + 1 + D, nchunks - 1), ra[d1], rb[d1]);
-        compute(cc & 1, cc);
-        if constexpr ((SCHED & NT_HINTS) != 0) {  // interleave: per MFMA, a few VALU / DS ops
+        compute(cc & 1);
 #pragma unroll
-          for (int i = 0; i < 4 * TM * (NPL == 3 ? 6 : 1) * (KC / 16); ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // VALU
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
-          }
+        for (int i = 0; i < 4; ++i) {  // interleave: per MFMA (4: one product per tile), a few VALU / DS ops
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
+          __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);  // VALU
+          __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
         }
       }
     }
@@ -377,50 +370,34 @@ __global__ __launch_bounds__(256) void gemm_nt_x3_kernel(NTArgs a, const uint4* 
         const int d1 = (d + 1) % D;
         __syncthreads();
         if (cc + 1 < nchunks) store(cc + 1, (cc + 1) & 1, ra[d1], rb[d1]);
-        compute(cc & 1, cc);
+        compute(cc & 1);
       }
     }
-    nt_epilogue<TM, CBF>(a, acc, m0, n0, lane, wave, seed);
-    return;
-  }
-  int c0 = 0;
-  for (; c0 + D <= nchunks; c0 += D) {
+  } else {
+    // the classic order: stage c; barrier; MFMAs of c
+    int c0 = 0;
+    for (; c0 + D <= nchunks; c0 += D) {
 #pragma unroll
-    for (int d = 0; d < D; ++d) {
+      for (int d = 0; d < D; ++d) {
+        const int c = c0 + d;
+        const int buf = c & 1;
+        store(c, buf, ra[d], rb[d]);  // buf last read by compute(c - 2): behind barrier c - 1
+        __syncthreads();
+        load(min(c + D, nchunks - 1), ra[d], rb[d]);
+        compute(buf);
+      }
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {  // tail: the last nchunks mod D chunks, already loaded
       const int c = c0 + d;
-      const int buf = c & 1;
-      store(c, buf, ra[d], rb[d]);  // buf last read by compute(c - 2): behind barrier c - 1
-      __syncthreads();
-      load(min(c + D, nchunks - 1), ra[d], rb[d]);
-      compute(buf, c);
+      if (c < nchunks) {
+        store(c, c & 1, ra[d], rb[d]);
+        __syncthreads();
+        compute(c & 1);
+      }
     }
   }
-#pragma unroll
-  for (int d = 0; d < D; ++d) {  // tail: the last nchunks mod D chunks, already loaded
-    const int c = c0 + d;
-    if (c < nchunks) {
-      store(c, c & 1, ra[d], rb[d]);
-      __syncthreads();
-      compute(c & 1, c);
-    }
-  }
-  nt_epilogue<TM, CBF>(a, acc, m0, n0, lane, wave, seed);
-}
-
-template <int KC, int TM, int AV, int AU, int D>
-void launch_nt_x3_b(const NTArgs& a, const uint4* bimg, hipStream_t st) {
-  dim3 grid((unsigned)ceil_div(a.M, 128 * TM), (unsigned)ceil_div(a.Nc, BN));
-  if (bimg) gemm_nt_x3_kernel<KC, TM, AV, AU, 0, D><<<grid, 256, 0, st>>>(a, bimg);
-  else if (a.wvec == 4) gemm_nt_x3_kernel<KC, TM, AV, AU, 4, D><<<grid, 256, 0, st>>>(a, nullptr);
-  else if (a.wvec == 2) gemm_nt_x3_kernel<KC, TM, AV, AU, 2, D><<<grid, 256, 0, st>>>(a, nullptr);
-  else gemm_nt_x3_kernel<KC, TM, AV, AU, 1, D><<<grid, 256, 0, st>>>(a, nullptr);
-}
-
-template <int KC, int TM, int D, int AU>
-void launch_nt_x3_a(const NTArgs& a, int av, const uint4* bimg, hipStream_t st) {
-  if (av == 4) launch_nt_x3_b<KC, TM, 4, (AU < 4 ? 4 : AU), D>(a, bimg, st);
-  else if (av == 2) launch_nt_x3_b<KC, TM, 2, AU, D>(a, bimg, st);
-  else launch_nt_x3_b<KC, TM, 1, AU, D>(a, bimg, st);
+  nt_epilogue<CBF>(a, acc, m0, n0, lane, wave, seed);
 }
 
 // ---- the in-kernel half-pair NT (GNN_MATH_HALF_PAIR, round 6): C = epi([A1 | A2] · [W1 | W2]ᵀ) for
@@ -452,7 +429,7 @@ __global__ __launch_bounds__(256) void gemm_nt_h2s_kernel(NTArgs a, const uint4*
     const float* A = c < nch1 ? a.a1 : a.a2;
     const int64_t lda = c < nch1 ? a.lda1 : a.lda2;
     const int k0 = (c < nch1 ? c : c - nch1) * KC;
-    x3_load_rows<AV, AU, KC, BM>(A, lda, m0, a.M, k0, KC, ra[c]);
+    x3_load_rows<AV, AU>(A, lda, m0, a.M, k0, KC, ra[c]);
   }
   const bool bon = threadIdx.x < 2 * NBC;          // slot 2n + khalf of a staged column
   typedef unsigned int u32x4v __attribute__((ext_vector_type(4)));  // (a plain vector: stays in registers)
@@ -486,17 +463,17 @@ __global__ __launch_bounds__(256) void gemm_nt_h2s_kernel(NTArgs a, const uint4*
       }
     }
   }
-  floatx16 acc[1][4];
+  floatx16 acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][t][r] = 0.0f;
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
   const int fr = (lane & 31) * P + 8 * (lane >> 5);
   const int bn = threadIdx.x >> 1, bkh = threadIdx.x & 1;
   static_for<NCH>([&](auto cc) __attribute__((always_inline)) {  // (static: ra / rb stay in registers)
     constexpr int c = decltype(cc)::value;
     constexpr int buf = c & 1;
-    h2_store_rows<AU, KC, BM, P>(As[buf], m0, a.M, KC, ra[c], asc);
+    h2_store_rows(As[buf], m0, a.M, KC, ra[c], asc);
     if (bon) {
 #pragma unroll
       for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x4v*>(&Bs[buf][p * BPL + bn * P + 8 * bkh]) = rb[buf][p];
@@ -512,49 +489,54 @@ __global__ __launch_bounds__(256) void gemm_nt_h2s_kernel(NTArgs a, const uint4*
 #pragma unroll
       for (int p = 0; p < 3; ++p) bf[t][p] = lds_frag16(Bs[buf] + fr + p * BPL + t * 32 * P);
 #pragma unroll
-    for (int t = 0; t < NTL; ++t) acc[0][t] = mfma_h2(af[0], af[1], bf[t][0], bf[t][1], bf[t][2], acc[0][t]);
+    for (int t = 0; t < NTL; ++t) acc[t] = mfma_h2(af[0], af[1], bf[t][0], bf[t][1], bf[t][2], acc[t]);
   });
   const float* csc = reinterpret_cast<const float*>(bimg + (int64_t)NCH * 3 * 256);
 #pragma unroll
   for (int t = 0; t < NTL; ++t) {  // undo the row and column scales (powers of two: exact)
     const float cs = csc[t * 32 + (lane & 31)];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[0][t][r] *= rsc[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)] * cs;
+    for (int r = 0; r < 16; ++r) acc[t][r] *= rsc[wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)] * cs;
   }
-  nt_epilogue<1, false>(a, acc, m0, 0, lane, wave, seed);
+  nt_epilogue(a, acc, m0, 0, lane, wave, seed);
 }
 
 // ------------------------------------------------------------------------------------- TN
 constexpr int TMC = 16;            // rows per chunk = one MFMA k-step
 constexpr int TP = TMC + 8;        // bf16 per transposed LDS row (12 dwords: conflict-free b128)
-constexpr int TGPL = 128 * TP;     // G plane: [n][m]
-constexpr int TAPL = KMAX * TP;    // A plane: [k][m]
 constexpr int TX_THREADS = 256;    // 4 waves, one per SIMD (512 registers each)
 constexpr int TX_AS = 3;           // A unit slots per thread (u = tid + 256·s < 768)
 
 // Staging: every thread owns TX_AS A slots and one G slot (plus a g slot for the g form with
 // MASK), each 8 consecutive rows of one column described by (base, ld, octet) and loaded by
-// the SAME straight-line code whatever the role, so the ring of D register stages keeps D-1
-// chunks of loads in flight across the store/barrier (a branch around a load would make the
-// compiler drain every stage).
+// the SAME straight-line code whatever the role, so the ring of D register stages keeps its
+// loads in flight across the store/barrier (a branch around a load would make the compiler drain
+// every stage).
 //   A slot s: u = tid + 256·s -> column k = u mod KP, rows 8·(u / KP) ..  if u < 2·KP, else idle
 //   G slot:   column n = tid mod 128, rows 8·(tid / 128) ..: h[:, n] (MASK) or g[:, n]
 // Idle slots load a fixed valid address.  dz (PROJ) is staged one chunk ahead into a 2-slot
 // LDS ring (16 rows x 4) by threads 0..63, so G(c) = (dz·P) ⊙ mask is formed at store(c)
 // from LDS instead of 32 registers of replicated dz rows per thread.
-// NPL = 3: f32 operands split (6 products).  NPL = 1: the bf16-storage path — A (ABF) and h
-// (HBF) are read as bf16, G is rounded to bf16, one product per MFMA.
-// HALFN (Nr <= 64): waves 0-1 / 2-3 take the two 32-row halves of the output for the first /
-// second half of the k-tiles (KT per wave), instead of waves 2-3 running MFMAs on all-zero rows.
+// ABF = false: f32 operands split (3 planes, 6 products).  ABF: the bf16-storage path — A (ABF) and
+// h (HBF) are read as bf16, G is rounded to bf16, one product per MFMA.
+// GOUT: the G write-out (gout, needed only when a further layer's dh follows).
+// KT: k-tiles per wave.  HALFN (Nr <= 64): waves 0-1 / 2-3 take the two 32-row halves of the output
+// for the first / second half of the k-tiles, instead of waves 2-3 running MFMAs on all-zero rows.
 // H2S (round 6, GNN_MATH_HALF_PAIR; the plain g form): the in-kernel half-pair form.  Before the
 // chunk loop (behind chunk 0's loads) the block takes E_A = max row_exp[r] over its rows (the
 // forward NT's row bounds of the same A) and E_G from max |g| over its rows (one pass, float4
 // pieces), stages A as f16 hi / lo of A·2^(14 − E_A) and G as hi' / hi / lo of G·2^(4 − E_G), runs
 // three products per k-tile, and writes acc·2^(E_A − 14)·2^(E_G − 15) to its slab (exact).
-template <bool PROJ, bool MASK, int D, int KT, int NPL = 3, bool ABF = false, bool HBF = false, int PIPE = 0,
-          bool GOUT = true, bool HALFN = false, bool H2S = false>
+// One chunk of loads is in flight across the store / barrier / MFMAs of the chunk before it, in the
+// classic order (launch_tn_x3: deeper rings and a pipelined order were measured and removed).
+template <bool PROJ, bool MASK, int KT, bool ABF, bool HBF, bool GOUT, bool HALFN, bool H2S>
 __device__ __forceinline__ void gemm_tn_split_body(const TNArgs& a) {
-  static_assert(!H2S || (!PROJ && !MASK && !GOUT && NPL == 3 && !ABF && PIPE == 0), "half-pair: plain g form, f32");
+  static_assert(!H2S || (!PROJ && !MASK && !GOUT && !ABF), "half-pair: plain g form, f32");
+  constexpr int NPL = ABF ? 1 : 3;                       // planes of G (and of A, but H2S)
+  // D: register stages of loads.  One: the d-loops below run once, and the chunk loop keeps its
+  // block-of-D-plus-tail shape — written as one plain loop the same kernels schedule differently
+  // (compared as assembly), and their code is kept as measured.
+  constexpr int D = 1;
   constexpr int NS = TX_AS + ((!PROJ && MASK) ? 2 : 1);  // + G slot (+ g slot)
   constexpr int GS = TX_AS;                              // the G slot index
   constexpr int APN = H2S ? 2 : NPL;                     // A planes (H2S: hi, lo; G keeps 3: hi', hi, lo)
@@ -872,43 +854,6 @@ __device__ __forceinline__ void gemm_tn_split_body(const TNArgs& a) {
     prologue();
     __syncthreads();  // Ps, dzL[0] (H2S: the scan partials)
     finish_scales();
-    if constexpr (PIPE != 0) {
-      // software-pipelined order: between two barriers, chunk c+1 is staged into the other
-      // buffers while chunk c's MFMAs run (PIPE == 2 adds interleave hints for the scheduler)
-      store(0, 0);
-      load(0, min(D, nch - 1));
-      int c = 0;
-      for (; c + D < nch; c += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          const int cc = c + d;
-          const int d1 = (d + 1) % D;
-          __syncthreads();
-          store(d1, cc + 1);
-          load(d1, min(cc + 1 + D, nch - 1));
-          compute(cc);
-          if constexpr (PIPE == 2) {
-#pragma unroll
-            for (int i = 0; i < KT * (NPL == 3 ? 6 : 1); ++i) {
-              __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
-              __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);  // DS read
-              __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // VALU
-              __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // DS write
-              __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);  // VMEM read
-            }
-          }
-        }
-      }
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        const int cc = c + d;
-        if (cc < nch) {
-          __syncthreads();
-          if (cc + 1 < nch) store((d + 1) % D, cc + 1);
-          compute(cc);
-        }
-      }
-    } else {
     int c0 = 0;
     for (; c0 + D <= nch; c0 += D) {
 #pragma unroll
@@ -929,7 +874,6 @@ __device__ __forceinline__ void gemm_tn_split_body(const TNArgs& a) {
         compute(c);
       }
     }
-    }
   }
 
   write_slab();
@@ -939,16 +883,24 @@ __device__ __forceinline__ void gemm_tn_split_body(const TNArgs& a) {
   side_write();
 }
 
-// the split-bf16 TN (NPL = 3: 6 products; NPL = 1: the bf16-storage form) and its in-kernel
-// half-pair form (GNN_MATH_HALF_PAIR), one body, two kernel names
-template <bool PROJ, bool MASK, int D, int KT, int NPL = 3, bool ABF = false, bool HBF = false, int PIPE = 0,
-          bool GOUT = true, bool HALFN = false>
+// the split-bf16 TN (6 products; ABF: the bf16-storage form, one) and its in-kernel half-pair form
+// (GNN_MATH_HALF_PAIR), one body, two kernel names
+template <bool PROJ, bool MASK, int KT, bool ABF, bool HBF, bool GOUT, bool HALFN>
 __global__ __launch_bounds__(TX_THREADS) void gemm_tn_x3_kernel(TNArgs a) {
-  gemm_tn_split_body<PROJ, MASK, D, KT, NPL, ABF, HBF, PIPE, GOUT, HALFN, false>(a);
+  gemm_tn_split_body<PROJ, MASK, KT, ABF, HBF, GOUT, HALFN, false>(a);
 }
 template <int KT, bool HALFN>
 __global__ __launch_bounds__(TX_THREADS) void gemm_tn_h2s_kernel(TNArgs a) {
-  gemm_tn_split_body<false, false, 1, KT, 3, false, false, 0, false, HALFN, true>(a);
+  gemm_tn_split_body<false, false, KT, false, false, false, HALFN, true>(a);
+}
+
+// f(KT, HALFN): the k-tiles per wave of the split TN kernels for a's K and N.  Nr <= 64 (GCN / GAT /
+// SAGE-ResBN hidden width 64): the half-N mapping, ceil(nkt / 2) k-tiles per wave
+template <typename F>
+void tn_kt_ladder(const TNArgs& a, F&& f) {
+  const int nkt = (a.k1 + a.k2 + 31) / 32;
+  if (a.Nr <= 64) with_rung<2, 3, 4, 6>((nkt + 1) / 2, [&](auto kt) { f(kt, std::true_type{}); });
+  else with_rung<6, 8, 11, 12>(nkt, [&](auto kt) { f(kt, std::false_type{}); });
 }
 
 }  // namespace
@@ -962,75 +914,53 @@ size_t nt_x3_workspace(int64_t k1, int64_t k2) {  // pre-split B image, 12 KB pe
 }
 
 void launch_nt_x3(const NTArgs& a, void* ws, size_t ws_bytes, hipStream_t st) {
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
-  auto av_ok = [&](int v) {
-    return (a.k1 % v == 0) && (a.lda1 % v == 0) && al(a.a1, 4 * v) &&
-           (a.k2 == 0 || ((a.k2 % v == 0) && (a.lda2 % v == 0) && al(a.a2, 4 * v)));
-  };
-  const uint4* bimg = nullptr;
-  if (a.a_bf16) {  // bf16 storage: one product per MFMA on bf16 operands (B rounded to bf16)
-    auto bv_ok = [&](int v) {
-      return (a.k1 % v == 0) && (a.lda1 % v == 0) && al(a.a1, 2 * v) &&
-             (a.k2 == 0 || ((a.k2 % v == 0) && (a.lda2 % v == 0) && al(a.a2, 2 * v)));
-    };
-    const bool pre = ws && ws_bytes >= nt_x3_workspace(a.k1, a.k2) && a.Nc <= BN;
-    if (pre) {
-      const int nch1 = (a.k1 + 15) / 16, nch = nch1 + (a.k2 + 15) / 16;
-      x3_presplit_b_kernel<<<nch, 256, 0, st>>>(a, static_cast<uint4*>(ws), nch1, nch);
-      bimg = static_cast<const uint4*>(ws);
-    }
-    dim3 grid((unsigned)ceil_div(a.M, 128), (unsigned)ceil_div(a.Nc, BN));
-#define GNN_NTB(AVV, BVV, C) gemm_nt_x3_kernel<16, 1, AVV, 2, BVV, 2, 1, true, C, BVV == 0 ? NT_PIPE | NT_HINTS : 0><<<grid, 256, 0, st>>>(a, bimg)
-#define GNN_NTB_C(AVV, BVV) do { if (a.c_bf16) GNN_NTB(AVV, BVV, true); else GNN_NTB(AVV, BVV, false); } while (0)
-    const bool v2 = bv_ok(2);
-    if (bimg) { if (v2) GNN_NTB_C(2, 0); else GNN_NTB_C(1, 0); }
-    else if (a.wvec >= 2) { if (v2) GNN_NTB_C(2, 2); else GNN_NTB_C(1, 2); }
-    else { if (v2) GNN_NTB_C(2, 1); else GNN_NTB_C(1, 1); }
-#undef GNN_NTB_C
-#undef GNN_NTB
-    return;
-  }
-  const int av = av_ok(4) ? 4 : (av_ok(2) ? 2 : 1);
   const bool pre = ws && ws_bytes >= nt_x3_workspace(a.k1, a.k2) && a.Nc <= BN;
   if (pre && nt_ws_ok(a)) {
-    // the weight-stationary persistent form (gemm_ws.hip, its own B image in `ws`)
+    // the weight-stationary persistent form (gemm_ws.hip, its own B image in `ws`; f32 A only)
     launch_nt_ws(a, static_cast<uint4*>(ws), st);
     return;
   }
+  const uint4* bimg = nullptr;
   if (pre) {
     const int nch1 = (a.k1 + 15) / 16, nch = nch1 + (a.k2 + 15) / 16;
     x3_presplit_b_kernel<<<nch, 256, 0, st>>>(a, static_cast<uint4*>(ws), nch1, nch);
     bimg = static_cast<const uint4*>(ws);
   }
+  // A rows can be read as vectors of v elements (4 bytes each, 2 when bf16)
+  auto av_ok = [&](int v) {
+    const int b = (a.a_bf16 ? 2 : 4) * v;
+    return (a.k1 % v == 0) && (a.lda1 % v == 0) && aligned(a.a1, b) &&
+           (a.k2 == 0 || ((a.k2 % v == 0) && (a.lda2 % v == 0) && aligned(a.a2, b)));
+  };
+  const dim3 grid((unsigned)ceil_div(a.M, XROWS), (unsigned)ceil_div(a.Nc, BN));
+  // B: the image (BV = 0), else W rows read as vectors of a.wvec = 4 | 2 floats, any other value as 1
+  const int bv = bimg ? 0 : a.wvec == 4 ? 4 : a.wvec == 2 ? 2 : 1;
+  if (a.a_bf16) {  // bf16 storage: one product per MFMA on bf16 operands (B rounded to bf16)
+    with_rung<1, 2>(av_ok(2) ? 2 : 1, [&](auto av) {
+      with_rung<0, 1, 2>(bv, [&](auto bvc) {  // (bf16 W pairs at the widest: BV = 4 runs as 2)
+        if (a.c_bf16) gemm_nt_x3_kernel<av(), bvc(), true, true><<<grid, 256, 0, st>>>(a, bimg);
+        else gemm_nt_x3_kernel<av(), bvc(), true, false><<<grid, 256, 0, st>>>(a, bimg);
+      });
+    });
+    return;
+  }
   // The classic order (stage c; barrier; MFMAs of c) for the shapes outside nt_ws_ok.  r05-r10 lab
   // (Elliptic layer-1 shape): pipelined order + sched_group_barrier interleave 155-159 us vs
   // classic 171-182; D = 1 / 3 ring 228 / 188; A fragments straight to registers 291; an LDS-DMA
-  // form 151-167; TM = 2 216-233 — the weight-stationary form (135 us) replaced them.
-  launch_nt_x3_a<16, 1, 2, 2>(a, av, bimg, st);
+  // form 151-167; two 32-row tiles per wave 216-233; 32-deep chunks no faster — the
+  // weight-stationary form (135 us) replaced them.
+  with_rung<1, 2, 4>(av_ok(4) ? 4 : av_ok(2) ? 2 : 1, [&](auto av) {
+    with_rung<0, 1, 2, 4>(bv, [&](auto bvc) {
+      gemm_nt_x3_kernel<av(), bvc(), false, false><<<grid, 256, 0, st>>>(a, bimg);
+    });
+  });
 }
 
-template <int D, int KT, int NPL = 3, bool ABF = false, bool HBF = false, int PIPE = 0, bool GO = false,
-          bool HN = false>
-void launch_tn_x3_kg(const TNArgs& a, int nblk, hipStream_t st) {
-  const bool proj = a.dz != nullptr, mask = a.h != nullptr;
-  if (proj && mask) gemm_tn_x3_kernel<true, true, D, KT, NPL, ABF, HBF, PIPE, GO, HN><<<nblk, TX_THREADS, 0, st>>>(a);
-  else if (proj) gemm_tn_x3_kernel<true, false, D, KT, NPL, ABF, HBF, PIPE, GO, HN><<<nblk, TX_THREADS, 0, st>>>(a);
-  else if (mask) gemm_tn_x3_kernel<false, true, D, KT, NPL, ABF, HBF, PIPE, GO, HN><<<nblk, TX_THREADS, 0, st>>>(a);
-  else gemm_tn_x3_kernel<false, false, D, KT, NPL, ABF, HBF, PIPE, GO, HN><<<nblk, TX_THREADS, 0, st>>>(a);
-}
-
-// the G write-out (gout, needed only when a further layer's dh follows) is a compile-time branch
-template <int D, int KT, int NPL = 3, bool ABF = false, bool HBF = false, int PIPE = 0, bool HN = false>
-void launch_tn_x3_k(const TNArgs& a, int nblk, hipStream_t st) {
-  if (a.gout) launch_tn_x3_kg<D, KT, NPL, ABF, HBF, PIPE, true, HN>(a, nblk, st);
-  else launch_tn_x3_kg<D, KT, NPL, ABF, HBF, PIPE, false, HN>(a, nblk, st);
-}
-
-
+// The classic order (stage c; barrier; MFMAs of c), one chunk of loads in flight.
 // Lab (MI355X, Elliptic layer-1 TN, dz form + mask, variants interleaved in one process): with the
 // staging VALU cut from ~530 to ~325 per chunk (unmasked A, row offsets by adds, no per-row masks
-// in the dz form) the classic order runs 156 us and the pipelined order with interleave hints
-// 183 (before the cuts: 207 vs 196).  A 32-row-chunk variant measured 217-227 and was removed.
+// in the dz form) the classic order runs 156 us and a software-pipelined order with interleave hints
+// (removed) 183 (before the cuts: 207 vs 196).  A 32-row-chunk variant measured 217-227 and was removed.
 // r08 (removed after measuring): a deeper load ring D = 2 / 3 in the classic order 166 / 159 us
 // vs 156; a wave-specialised form (512 threads: 4 producer waves stage chunk c + 1 while 4
 // consumer waves run chunk c's MFMAs, one barrier per chunk, 218-230 VGPRs, no spills) 150 / 148
@@ -1043,27 +973,24 @@ void launch_tn_x3_k(const TNArgs& a, int nblk, hipStream_t st) {
 // (not HBM-bound); two waves per SIMD (512 threads, half the k-tiles per wave, 2 A slots + a
 // 4-row G slot per thread) 164.  Every form lands at ~6,000 cycles per chunk per SIMD.
 void launch_tn_x3(const TNArgs& a, int nblk, hipStream_t st) {
-  const int nkt = (a.k1 + a.k2 + 31) / 32;
-  constexpr int D = 1;
-  if (a.a_bf16) {
-    if (nkt <= 8) { if (a.h_bf16) launch_tn_x3_k<D, 8, 1, true, true, 0>(a, nblk, st); else launch_tn_x3_k<D, 8, 1, true, false, 0>(a, nblk, st); }
-    else { if (a.h_bf16) launch_tn_x3_k<D, 12, 1, true, true, 0>(a, nblk, st); else launch_tn_x3_k<D, 12, 1, true, false, 0>(a, nblk, st); }
+  if (a.a_bf16) {  // the bf16-storage form; h read as bf16 where the kernel reads h at all
+    with_rung<8, 12>((a.k1 + a.k2 + 31) / 32, [&](auto kt) {
+      tn_forms(a, [&](auto proj, auto mask, auto gout) {
+        if constexpr (mask()) {
+          if (a.h_bf16) gemm_tn_x3_kernel<proj(), true, kt(), true, true, gout(), false><<<nblk, TX_THREADS, 0, st>>>(a);
+          else gemm_tn_x3_kernel<proj(), true, kt(), true, false, gout(), false><<<nblk, TX_THREADS, 0, st>>>(a);
+        } else {
+          gemm_tn_x3_kernel<proj(), false, kt(), true, false, gout(), false><<<nblk, TX_THREADS, 0, st>>>(a);
+        }
+      });
+    });
     return;
   }
-  // production: classic order (stage c; barrier; MFMAs of c).  Nr <= 64 (GCN / GAT / SAGE-ResBN
-  // hidden width 64): the half-N mapping, ceil(nkt / 2) k-tiles per wave
-  if (a.Nr <= 64) {
-    const int kh = (nkt + 1) / 2;
-    if (kh <= 2) launch_tn_x3_k<D, 2, 3, false, false, 0, true>(a, nblk, st);
-    else if (kh <= 3) launch_tn_x3_k<D, 3, 3, false, false, 0, true>(a, nblk, st);
-    else if (kh <= 4) launch_tn_x3_k<D, 4, 3, false, false, 0, true>(a, nblk, st);
-    else launch_tn_x3_k<D, 6, 3, false, false, 0, true>(a, nblk, st);
-    return;
-  }
-  if (nkt <= 6) launch_tn_x3_k<D, 6, 3, false, false, 0>(a, nblk, st);
-  else if (nkt <= 8) launch_tn_x3_k<D, 8, 3, false, false, 0>(a, nblk, st);
-  else if (nkt <= 11) launch_tn_x3_k<D, 11, 3, false, false, 0>(a, nblk, st);
-  else launch_tn_x3_k<D, 12, 3, false, false, 0>(a, nblk, st);
+  tn_kt_ladder(a, [&](auto kt, auto halfn) {
+    tn_forms(a, [&](auto proj, auto mask, auto gout) {
+      gemm_tn_x3_kernel<proj(), mask(), kt(), false, false, gout(), halfn()><<<nblk, TX_THREADS, 0, st>>>(a);
+    });
+  });
 }
 
 // ---- the in-kernel half-pair forms (GNN_MATH_HALF_PAIR)
@@ -1086,9 +1013,8 @@ void launch_nt_h2s(const NTArgs& a, void* ws, hipStream_t st) {
   p.colscale = reinterpret_cast<float*>(p.img + (size_t)nch * 3 * 256);
   p.a_unscale = 1.0f;  // (the A scales are per row, undone in the kernel's epilogue)
   launch_prep_h2(p, st);
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
-  const bool v4 = (a.lda1 % 4 == 0) && al(a.a1, 16) && (a.k2 == 0 || ((a.lda2 % 4 == 0) && al(a.a2, 16)));
-  const bool v2 = (a.lda1 % 2 == 0) && al(a.a1, 8) && (a.k2 == 0 || ((a.lda2 % 2 == 0) && al(a.a2, 8)));
+  const bool v4 = (a.lda1 % 4 == 0) && aligned(a.a1, 16) && (a.k2 == 0 || ((a.lda2 % 4 == 0) && aligned(a.a2, 16)));
+  const bool v2 = (a.lda1 % 2 == 0) && aligned(a.a1, 8) && (a.k2 == 0 || ((a.lda2 % 2 == 0) && aligned(a.a2, 8)));
   const dim3 grid((unsigned)ceil_div(a.M, 128));
   const uint4* img = p.img;
 #define GNN_H2S_V(NCHV, NTLV)                                                                  \
@@ -1113,25 +1039,12 @@ void launch_nt_h2s(const NTArgs& a, void* ws, hipStream_t st) {
 }
 
 bool tn_h2s_ok(const TNArgs& a) {
-  auto al = [](const void* q, int b) { return (reinterpret_cast<uintptr_t>(q) % b) == 0; };
   return a.rowexp && !a.dz && !a.h && !a.gout && a.g && !a.a_bf16 && !a.g_bf16 && a.Nr % 4 == 0 && a.Nr <= 128 &&
-         a.ldg % 4 == 0 && al(a.g, 16) && a.k1 + a.k2 <= KMAX && a.M >= 16;
+         a.ldg % 4 == 0 && aligned(a.g, 16) && a.k1 + a.k2 <= KMAX && a.M >= 16;
 }
 
 void launch_tn_h2s(const TNArgs& a, int nblk, hipStream_t st) {
-  const int nkt = (a.k1 + a.k2 + 31) / 32;
-#define GNN_TNH(KTV, HN) gemm_tn_h2s_kernel<KTV, HN><<<nblk, TX_THREADS, 0, st>>>(a)
-  if (a.Nr <= 64) {  // the half-N mapping (as launch_tn_x3)
-    const int kh = (nkt + 1) / 2;
-    if (kh <= 2) GNN_TNH(2, true);
-    else if (kh <= 3) GNN_TNH(3, true);
-    else if (kh <= 4) GNN_TNH(4, true);
-    else GNN_TNH(6, true);
-  } else if (nkt <= 6) GNN_TNH(6, false);
-  else if (nkt <= 8) GNN_TNH(8, false);
-  else if (nkt <= 11) GNN_TNH(11, false);
-  else GNN_TNH(12, false);
-#undef GNN_TNH
+  tn_kt_ladder(a, [&](auto kt, auto halfn) { gemm_tn_h2s_kernel<kt(), halfn()><<<nblk, TX_THREADS, 0, st>>>(a); });
 }
 
 }  // namespace gnnmp

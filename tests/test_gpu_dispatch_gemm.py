@@ -13,7 +13,7 @@ one operand at a time sits at an 8- or 4-byte aligned pointer or on a padded pit
   gemm_f32.hip     gemm_nt_dispatch   v4 / v2 / scalar A loads, wvec (w1 / w2), bvec4 (bt)
                    gemm_tn_kernel     v2 / scalar A loads, the dz form's 16-byte dz row load
   gemm_x3.hip      launch_nt_x3       nt_ws_ok (gemm_ws.hip: dense 16-byte A, 16-byte C) or the
-                                      classic kernel at av = 4 | 2 | 1
+                                      classic gemm_nt_x3_kernel<AV, BV, ABF, CBF> at AV = 4 | 2 | 1
                    launch_nt_h2s      v4 / v2 / scalar A staging (math="half_pair")
                    tn_h2s_ok          16-byte g with ldg % 4 == 0, else the split-bf16 TN
   gemm_planes.hip  tn_h2_ok (g form)  16-byte g with ldg % 4 == 0, else the split-bf16 image TN
@@ -342,6 +342,223 @@ def test_gemm_tn_half_pair_alignment(device, M, k1, k2, nr, l1, l2, lg):
 
 
 # ------------------------------------------------------------------------------- image-A TN gates
+# (nr, k1 + k2, KT): every rung of tn_kt_ladder (gemm_x3.hip), which launch_tn_x3 and launch_tn_h2s
+# share.  nkt = ceil(K / 32) k-tiles; nr > 64: KT = the first of 6 / 8 / 11 / 12 >= nkt; nr <= 64 (the
+# half-N mapping): KT = the first of 2 / 3 / 4 / 6 >= ceil(nkt / 2)
+KT_RUNGS = [(128, 192, 6), (128, 256, 8), (128, 352, 11), (128, 384, 12),
+            (64, 128, 2), (64, 192, 3), (64, 256, 4), (64, 384, 6)]
+
+
+@pytest.mark.parametrize("math", ["split_bf16", "half_pair"])
+@pytest.mark.parametrize("nr,K,kt", KT_RUNGS, ids=[f"N{c[0]}-K{c[1]}-KT{c[2]}" for c in KT_RUNGS])
+def test_gemm_tn_kt_rungs(device, nr, K, kt, math):
+    """gemm_tn_x3_kernel / gemm_tn_h2s_kernel (the plain g form) at each k-tile count their shared
+    ladder picks, 80 rows.  test_gemm_tn_alignment's bound for the split-bf16 TN, and
+    test_gemm_tn_half_pair_alignment's for the half-pair one (its row_exp formed here as the NT
+    defines it: max |A[r, :]| < 2^E_r)."""
+    from elliptic_gnn_project_amd.fused import gemm_tn
+
+    nkt = -(-K // 32)
+    assert kt == next(v for v in ((2, 3, 4, 6) if nr <= 64 else (6, 8, 11, 12)) if v >= (-(-nkt // 2) if nr <= 64 else nkt))
+    M, k2 = 80, 64
+    a1, a2, _, _, A = _operands(M, K - k2, k2, 1, nr + K)
+    G = torch.randn(M, nr, generator=torch.Generator().manual_seed(nr + K + 1))
+    kw = {}
+    if math == "half_pair":
+        kw["row_exp"] = torch.frexp(A.abs().amax(1)).exponent.to(torch.int32).to(device)
+    dW, db, _, _ = gemm_tn(nr, a1.to(device), a2.to(device), g=G.to(device), math=math, **kw)
+    bound = 1e-5 if math == "split_bf16" else 1e-6
+    assert rel_l2(torch.cat([dW[0], dW[1]], 1), G.double().t() @ A.double()) < bound
+    assert rel_l2(db, G.double().sum(0)) < bound
+
+
+# ------------------------------------------------------------------------------- ladder rungs
+# The launchers share their ladders (gemm_common.hpp with_rung / tn_forms, gemm_ws.hip with_nt_epi);
+# the cases below are the rungs no other GEMM test launches, each at the bound the test it cites
+# applies to the same kernel.
+
+@pytest.mark.parametrize("math", ["f32", "split_bf16"])
+@pytest.mark.parametrize("with_gout", [False, True])
+def test_gemm_tn_dz_form_without_mask(device, with_gout, math):
+    """tn_forms' PROJ, no MASK rungs on the generic TNs (gemm_tn_kernel<true, false, ..>,
+    gemm_tn_x3_kernel<true, false, .., GOUT, ..>): G = dz·P with no h.  test_gemm_tn_alignment's bounds."""
+    from elliptic_gnn_project_amd.fused import gemm_tn
+
+    M, nr, k1, k2 = 80, 64, 64, 64
+    a1, a2, _, _, A = _operands(M, k1, k2, 1, 71)
+    g_ = torch.Generator().manual_seed(72)
+    dz = torch.randn(M, 4, generator=g_)
+    proj = torch.randn(4, nr, generator=g_)
+    G = dz.double() @ proj.double()
+    gout = torch.empty(M, nr, device=device) if with_gout else None
+    dW, db, _, dzs = gemm_tn(nr, a1.to(device), a2.to(device), dz=dz.to(device), proj=proj.to(device), gout=gout,
+                             math=math)
+    if with_gout:
+        torch.testing.assert_close(gout.cpu().double(), G, rtol=1e-5, atol=1e-5)
+    assert rel_l2(torch.cat([dW[0], dW[1]], 1), G.t() @ A.double()) < 1e-5
+    assert rel_l2(db, G.sum(0)) < 1e-5
+    assert rel_l2(dzs, dz.double().sum(0)) < 1e-5
+
+
+def _split_image(a, x, device, half_pair=False):  # test_gpu_planes._image / test_gpu_h2._image
+    from elliptic_gnn_project_amd import _lib
+    from elliptic_gnn_project_amd.planes import HalfPairImage, SplitImage
+
+    im = (HalfPairImage if half_pair else SplitImage)(a.size(0), a.size(1), x.size(1), device)
+    im.fill_x(x.to(device))
+    _lib.call("gnn_split_h2_f32" if half_pair else "gnn_split_planes_f32", a.to(device).data_ptr(), a.size(1), im.n,
+              im.k1, im.ptr, im.ld, im.ps, 0, im.col2, *((im.exp,) if half_pair else ()), _lib.stream_handle(device))
+    return im
+
+
+# (k per operand, nr, form, gout): image rows of 128 (KT = 4) and 240 (KT = 8) bf16, the forms of
+# tn_forms that test_gpu_planes.py leaves out, and the N <= 64 split-K mapping with gout
+TN_PLANES_RUNGS = [(60, 128, "dz", False), (120, 128, "dz", True), (120, 64, "g", True), (60, 128, "dz_mask", True)]
+
+
+@pytest.mark.parametrize("k,nr,form,with_gout", TN_PLANES_RUNGS,
+                         ids=[f"k{c[0]}-N{c[1]}-{c[2]}-{'gout' if c[3] else 'nogout'}" for c in TN_PLANES_RUNGS])
+def test_gemm_tn_planes_rungs(device, k, nr, form, with_gout):
+    """gemm_tn_planes_kernel at KT = 4 / 8 (launch_tn_planes' ladder over the image width) and at the
+    PROJ / MASK / GOUT forms test_gpu_planes.py does not launch.  test_tn_planes_vs_f64's bounds."""
+    from elliptic_gnn_project_amd.fused import gemm_tn
+
+    M = 80
+    g_ = torch.Generator().manual_seed(k + nr)
+    a1, a2 = torch.randn(M, k, generator=g_), torch.randn(M, k, generator=g_)
+    h = torch.relu(torch.randn(M, nr, generator=g_))
+    dz = torch.randn(M, 4, generator=g_) * 1e-3
+    proj = torch.randn(4, nr, generator=g_)
+    G = torch.randn(M, nr, generator=g_) * 1e-3
+    if form == "g":
+        kw = dict(g=G.to(device))
+    else:
+        G = dz @ proj
+        kw = dict(dz=dz.to(device), proj=proj.to(device))
+    if form == "dz_mask":
+        G = torch.where(h > 0, G * 2.0, torch.zeros_like(G))
+        kw.update(h=h.to(device), hscale=2.0)
+    gout = torch.empty(M, nr, device=device) if with_gout else None
+    im = _split_image(a1, a2, device)
+    assert (im.ld + 31) // 32 == (4 if k == 60 else 8)
+    assert gemm_tn(nr, None, None, planes=im, check_planes=True, gout=gout, **kw)
+    dW, db, dW2, dzs = gemm_tn(nr, None, None, planes=im, gout=gout, **kw)
+    assert rel_l2(torch.cat([dW[0], dW[1]], 1), G.double().t() @ torch.cat([a1, a2], 1).double()) < 1e-6
+    assert rel_l2(db, G.double().sum(0)) < 1e-6
+    if form != "g":
+        assert rel_l2(dzs, dz.double().sum(0)) < 1e-6
+    if form == "dz_mask":
+        assert rel_l2(dW2, dz.double().t() @ h.double()) < 1e-6
+    if with_gout:
+        torch.testing.assert_close(gout.cpu(), G, rtol=1e-6, atol=1e-9)
+
+
+@pytest.mark.parametrize("image,epi", [("split", "bias_relu"), ("half_pair", "bias_relu"), ("half_pair", "keep_bits")])
+def test_gemm_nt_image_epilogue_rungs(device, image, epi):
+    """with_nt_epi's rungs the image NT tests leave out: bias + ReLU alone on gemm_nt_planes_kernel and
+    gemm_nt_h2_kernel, and the half-pair form's dropout from precomputed keep bits without the
+    projection.  test_nt_planes_vs_f64's / test_nt_h2_vs_f64's bound."""
+    from oracle.dropout_hash import keep_mask
+    from elliptic_gnn_project_amd.fused import gemm_nt
+
+    M, F, n, p, seed = 80, 166, 128, 0.5, 99
+    g_ = torch.Generator().manual_seed(len(image) + len(epi))
+    agg, x = torch.randn(M, F, generator=g_) * 0.7, torch.randn(M, F, generator=g_)
+    w1, w2 = torch.randn(n, F, generator=g_) * 0.08, torch.randn(n, F, generator=g_) * 0.08
+    bias = torch.randn(n, generator=g_) * 0.1
+    ref = torch.relu(torch.cat([agg, x], 1).double() @ torch.cat([w1, w2], 1).double().t() + bias.double())
+    kw = dict(w1=w1.to(device), w2=w2.to(device), bias=bias.to(device), relu=True)
+    if epi == "keep_bits":
+        keep = torch.from_numpy(keep_mask(seed, M, n, p)).to(torch.int64)
+        ref = ref * keep.double() * 2.0
+        # bit c of word c / 32 of a row (NTArgs::kmask)
+        words = (keep.view(M, 4, 32) << torch.arange(32)).sum(2)
+        words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+        kw.update(dropout_p=p, seed=seed, keep_mask=words.to(device))
+    im = _split_image(agg, x, device, half_pair=image == "half_pair")
+    assert gemm_nt(None, None, n, planes=im, check_planes=True, **kw)
+    c = gemm_nt(None, None, n, planes=im, **kw)
+    assert rel_l2(c, ref) < 1e-6
+
+
+@pytest.mark.parametrize("lw1,lw2,wvec", [("a16", "a16", 4), ("p8", "a16", 2), ("a16", "p4", 1)])
+def test_gemm_nt_x3_without_b_image(device, lw1, lw2, wvec):
+    """gemm_nt_x3_kernel<AV, BV = 4 | 2 | 1, ..>: with a workspace too small for the B image the kernel
+    splits W in place, at the widest vector its rows allow.  test_gemm_nt_weight_alignment's bound."""
+    from elliptic_gnn_project_amd.fused import gemm_nt
+
+    M, k1, k2, n = 80, 64, 64, 64
+    assert wvec == _vec([(k1, LAY[lw1]), (k2, LAY[lw2])])
+    a1, a2, W, bias, A = _operands(M, k1, k2, n, 73)
+    w1, w2 = _carve(W[:, :k1], LAY[lw1], device), _carve(W[:, k1:], LAY[lw2], device)
+    c = gemm_nt(a1.to(device), None, n, a2=a2.to(device), w1=w1.view, w2=w2.view, bias=bias.to(device),
+                math="split_bf16", workspace=torch.empty(1, device=device))
+    _done([w1, w2])
+    torch.testing.assert_close(c.cpu().double(), A.double() @ W.double().t() + bias.double(), rtol=1e-5, atol=1e-5)
+
+
+def _rb(t):  # test_gpu_bf16.rb
+    return t.to(torch.bfloat16).to(t.dtype)
+
+
+# (A one element off 4 bytes, B image, w1 layout, C dtype): AV = 1 | 2, BV = 0 | 2 | 1, CBF
+NT_BF16_RUNGS = [(True, True, "a16", "bf16"), (False, True, "a16", "f32"), (False, False, "a16", "f32"),
+                 (False, False, "p4", "bf16"), (True, False, "p4", "f32")]
+
+
+@pytest.mark.parametrize("odd,image,lw,cdt", NT_BF16_RUNGS,
+                         ids=[f"av{1 if c[0] else 2}-{'img' if c[1] else 'w'}-{c[2]}-{c[3]}" for c in NT_BF16_RUNGS])
+def test_gemm_nt_bf16_rungs(device, odd, image, lw, cdt):
+    """The bf16-storage gemm_nt_x3_kernel<AV, BV, true, CBF> off test_gemm_nt_bf16's one form (AV = 2, the
+    B image, bf16 C): A at a 2-byte aligned pointer, W split in place, f32 C.  test_gemm_nt_bf16's
+    global ceiling and relative L2 bound."""
+    from elliptic_gnn_project_amd.fused import gemm_nt
+
+    M, k1, k2, n = 80, 64, 64, 64
+    a1, a2, W, bias, _ = _operands(M, k1, k2, n, 74)
+    a1, a2 = a1.to(torch.bfloat16), a2.to(torch.bfloat16)
+
+    def place(t):  # bf16 rows at a 4-byte (flat allocation) or a 2-byte aligned pointer
+        buf = torch.empty(t.numel() + 2, dtype=torch.bfloat16, device=device)
+        v = buf[1 if odd else 2:][:t.numel()].view_as(t)
+        v.copy_(t)
+        return v
+
+    w1, w2 = _carve(W[:, :k1], LAY[lw], device), _carve(W[:, k1:], LAY["a16"], device)
+    out = torch.empty(M, n, dtype=torch.bfloat16 if cdt == "bf16" else torch.float32, device=device)
+    c = gemm_nt(place(a1), None, n, a2=place(a2), w1=w1.view, w2=w2.view, bias=bias.to(device), out=out,
+                **({} if image else dict(workspace=torch.empty(1, device=device))))
+    _done([w1, w2])
+    ref = torch.cat([a1, a2], 1).double() @ _rb(W).double().t() + bias.double()
+    d = (c.double().cpu() - ref).abs()
+    assert float(d.max()) <= float((2.0 ** -8 * ref.abs() + 1e-5).max()), float(d.max())
+    assert rel_l2(c, ref) < 3e-3
+
+
+@pytest.mark.parametrize("form", ["g", "g_mask"])
+@pytest.mark.parametrize("k", [128, 166], ids=["KT8", "KT12"])
+def test_gemm_tn_bf16_rungs(device, k, form):
+    """The bf16-storage gemm_tn_x3_kernel<.., KT = 8 | 12, true, HBF = false, ..>: no h, and an f32 h
+    (test_gemm_tn_bf16 gives a bf16 h).  Its bounds: G rounded to bf16 is the MFMA operand."""
+    from elliptic_gnn_project_amd.fused import gemm_tn
+
+    M, nr = 80, 128
+    g_ = torch.Generator().manual_seed(k)
+    a1 = torch.randn(M, k, generator=g_).to(torch.bfloat16)
+    a2 = torch.randn(M, k, generator=g_).to(torch.bfloat16)
+    h = torch.relu(torch.randn(M, nr, generator=g_))
+    g = torch.randn(M, nr, generator=g_) * 1e-3
+    G, kw = g, {}
+    if form == "g_mask":
+        kw = dict(h=h.to(device), hscale=2.0)
+        G = torch.where(h > 0, g * 2.0, torch.zeros_like(g))
+    gout = torch.empty(M, nr, device=device)
+    dW, db, _, _ = gemm_tn(nr, a1.to(device), a2.to(device), g=g.to(device), gout=gout, **kw)
+    torch.testing.assert_close(gout.cpu(), G, rtol=1e-5, atol=1e-8)
+    assert rel_l2(torch.cat([dW[0], dW[1]], 1), _rb(G).double().t() @ torch.cat([a1, a2], 1).double()) < 1e-5
+    assert rel_l2(db, G.sum(0)) < 1e-5
+
+
 @pytest.mark.parametrize("lg,h2_takes", [("a16", True), ("p8", False), ("p4", False), ("ld+2", False), ("pad16", True)])
 @pytest.mark.parametrize("nr", [64, 128])
 def test_gemm_tn_image_g_alignment(device, nr, lg, h2_takes):

@@ -14,7 +14,8 @@ The dispatch, restated from gemm_ws.hip as read (``nt_ws_ok``, ``nks_of``, ``ks_
 nt_ws_ok takes f32 operands with dense even-k segments, 16-byte C rows, Nc % 4 == 0, 64 < Nc <= 128,
 M >= 32, ceil((k1 + k2) / 16) in {8, 11, 16, 21} and an epilogue among plain | bias | bias + ReLU |
 bias + ReLU + dropout, the last two with or without the projection; launch_nt_ws splits K over a
-wave pair (KS = 2) except at 21 k-steps; launch_ws_k picks EPI from (proj, dropout, relu, bias).
+wave pair (KS = 2) except at 21 k-steps; with_nt_epi (shared by the four
+weight-stationary NT launchers) picks EPI from (proj, dropout, relu, bias).
 
 The checkers (``check``, ``check_z``), u = 2^-24, D = |A| |W|^T and b the bias:
  1. ceiling: |c - ref| <= (96 NKS + 4) 2^-23 1.01 (D + |b|) / (1 - p).  At most 96 NKS accumulations
@@ -70,7 +71,7 @@ def ks_of(nks):
 
 
 def epi_flags(epi):
-    """launch_ws_k: the EPI template argument of an epilogue (bias, relu, dropout, proj)."""
+    """with_nt_epi (gemm_ws.hip): the EPI template argument of an epilogue (bias, relu, dropout, proj)."""
     bias, relu, drop, proj = EPIS[epi]
     if proj and drop:
         return WS_BIAS | WS_RELU | WS_DROP | WS_PROJ
